@@ -8,7 +8,9 @@ the reference's GPT-2-small DAG (99 tasks each, batch 1 x 512 tokens — test_gp
 random-init bf16 weights, synthetic token ids. Weak scaling: one 512-token request per GPU.
 ``value`` is the step makespan in ms (max over ranks); lower is better.
 
-The same JSON line also carries (unless ``--no-extras``):
+A plain run does only what that figure needs: it sets up, warms up, times the steps, writes the
+step's outputs if ``--dump-outputs DIR`` is given, and prints the line. With ``--full`` the
+same JSON line also carries:
   * ``capped``: the reference's experiment (simulation.py:161-192, 375-376: regime 0.8, its
     0.5 GB-per-parameter cost model, schedulers.py:404-442 eviction) EXECUTED — ONE GPT-2 DAG
     spread over the N GPUs with the reference's node memory split, for MRU_spec, EFT and DFS:
@@ -17,10 +19,12 @@ The same JSON line also carries (unless ``--no-extras``):
     ``capped_replica`` (one request per GPU, each capped at 80 % of one DAG's need);
   * ``strong``: strong scaling with real cross-GPU DAG edges — a fixed batch of 8 GPT-2
     micro-batches pipeline-placed over the N GPUs (contiguous layer blocks; every block
-    boundary an RCCL p2p send/recv): ms per step, cross-GPU edges and bytes;
-  * ``rccl_world`` and ``per_rank_ms`` of the headline run.
+    boundary an RCCL p2p send/recv): ms per step, cross-GPU edges and bytes.
+Every line carries ``rccl_world`` and ``per_rank_ms`` of the headline run.
 
     python bench.py --gpus N --steps K --warmup W      # N > 1: starts its own N rank processes
+    python bench.py --full                              # ... plus the capped / strong sub-results
+    python bench.py --dump-outputs DIR                  # the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
     python bench.py --model gpt2-medium --gpus 2 --cap-gb 8 --replicas 1          # one DAG across 2 GPUs
     python bench.py --model mixtral-8x7b --gpus 8 --placement expert               # DP attention + experts over 8 GPUs
@@ -98,6 +102,39 @@ def _cache_policy() -> dict:
     return {"lm_head": ops.LMHEAD_POL, "gemm": ops.ACT_POL, "attention_flags": ops.ATTN_FLAGS}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs run, over all ranks (limit: 64 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(plan, ex, out_dir: str) -> list:
+    """``--dump-outputs``: what the step just run hands its caller — the output of every task of
+    the DAG that no other task consumes (each request's logits), as this rank holds it — written
+    as ``out_dir/<task id, "/" as ".">.npy`` in float32. An output larger than its share of the
+    byte budget is written as a fixed sample of its elements (flat indices drawn once from a
+    seeded generator, sorted), the same from run to run and from build to build."""
+    import numpy as np
+
+    consumed = {d for t in plan.tasks for d in t.dependencies}
+    names = [t.id for t in plan.tasks if t.id not in consumed]
+    if not names:
+        return []
+    os.makedirs(out_dir, exist_ok=True)
+    share = max(1, DUMP_BUDGET_BYTES // 4 // len(names))  # float32 elements per output
+    written = []
+    for name in names:
+        if not ex.owns_output(name):
+            continue  # another rank's output (or a task the memory cap left unplaced)
+        v = ex.output(name).detach().reshape(-1)
+        if v.numel() > share:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, v.numel(), (share,), generator=g).sort().values
+            v = v[idx.to(v.device)]
+        path = os.path.join(out_dir, name.replace("/", ".") + ".npy")
+        np.save(path, v.float().cpu().numpy())
+        written.append(path)
+    return written
+
+
 def launch_ranks(n: int) -> int:
     """``python bench.py --gpus N`` without a launcher: start N rank processes of this script
     (fresh children — nothing here has touched the GPU), one per GPU, rendezvous on 127.0.0.1;
@@ -133,7 +170,8 @@ def launch_ranks(n: int) -> int:
 
 def run(ctx: Ctx, steps: int, warmup: int, *, model, scheduler, cap_gb, replicas, batch, seq, cost_model,
         placement, tp=1, sp=1, fuse=True, use_graph=True, init="auto", refine=False, roctx=False,
-        profile=False, trace_out=None, tag="", node_speeds=None, merge_mb=1, transport=None) -> dict:
+        profile=False, trace_out=None, tag="", node_speeds=None, merge_mb=1, transport=None,
+        dump_dir=None) -> dict:
     """Plan, build the rank's executor, warm up, time ``steps`` steps bracketed by a barrier +
     device synchronize on both sides; the step time is the MAX over ranks."""
     t0 = time.time()
@@ -214,6 +252,8 @@ def run(ctx: Ctx, steps: int, warmup: int, *, model, scheduler, cap_gb, replicas
         "ep_overflow": [int(v) for v in ep_over],
         "cross_gpu_bytes_rccl": st.get("cross_gpu_bytes_rccl"),
     }
+    if dump_dir:
+        log(f"[bench{tag}] rank {ctx.rank}: outputs of the last timed step: {dump_outputs(plan, ex, dump_dir)}")
     if profile or trace_out:
         s = ex.step(profile=True)
         if trace_out:
@@ -339,7 +379,14 @@ def main():
                     help="before timing, pick GEMM configs by whole-step hipGraph time (persists ops/gemm_tuning.json)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-fuse", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (no capped / strong sub-results)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the capped / strong sub-results (off by default: a "
+                         "plain run measures the headline only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="headline only: the default, kept for older command lines (overrides --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one (every request's logits; "
+                         "a fixed seeded sample of an output too large for the 64 MB limit) as DIR/<name>.npy")
     ap.add_argument("--extra-steps", type=int, default=10, help="timed steps of each capped / strong sub-run")
     ap.add_argument("--strong-mb", type=int, default=8, help="micro-batches of the strong-scaling pipeline run")
     ap.add_argument("--no-strong-merge", dest="strong_merge", action="store_false",
@@ -396,7 +443,7 @@ def main():
                   use_graph=not args.no_graph)
     head = run(ctx, args.steps, args.warmup, scheduler=args.scheduler, cap_gb=args.cap_gb, replicas=replicas,
                cost_model=args.cost_model, placement=args.placement, tp=args.tp, sp=args.sp, init=args.init,
-               merge_mb=args.merge_mb,
+               merge_mb=args.merge_mb, dump_dir=args.dump_outputs,
                refine=args.refine_tuning, roctx=args.roctx, profile=args.profile, trace_out=args.trace_out, **common)
 
     emitted = threading.Lock()  # ONE line per job: whichever of the main thread / watchdog gets it
@@ -490,9 +537,10 @@ def main():
                 os._exit(0)
 
     t_extras = time.time()
-    if not args.no_extras:
+    full = args.full and not args.no_extras
+    if full:
         threading.Thread(target=watchdog, daemon=True).start()
-    if not args.no_extras:
+    if full:
         ew = min(args.warmup, 2)
         # the reference's experiment (simulation.py:161-192, 375-376), executed: ONE request DAG
         # spread over the N GPUs under its 80 % memory regime — the regime's memory split over the

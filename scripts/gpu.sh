@@ -2,10 +2,10 @@
 # The GPU jobs of this repo, by name (run on the box: gpurun -- 'bash scripts/gpu.sh JOB [ARGS]').
 # Every GPU step runs under its own time limit and the first failure ends the job.
 #
-#   suite                 full GPU test suite + smoke() + the driver's bench line
+#   suite                 full GPU test suite + smoke() + the bench line with its sub-results (bench.py --full)
 #   tests  PYTEST_ARGS    selected GPU tests (e.g. tests/test_loopback.py)
 #   bench  [N] [ARGS]     N runs of `bench.py --steps 200 --warmup 10 --no-extras ARGS`, ms per run
-#   line   [ARGS]         one full driver bench line (extras included) -> gpurun_out/<tag>/bench.json
+#   line   [ARGS]         one bench line with its sub-results (bench.py --full ARGS) -> bench.json in the output folder
 #   prof   MODEL [ARGS]   rocprofv3 kernel trace + per-dispatch breakdown of MODEL's step
 #   pmc    COUNTERS CMD   one rocprofv3 --pmc pass (<= the per-block counter limits) over CMD
 #   ab     VAR A B [ARGS] alternating bench runs under two values of an environment variable
@@ -33,7 +33,7 @@ case "$job" in
     tail -5 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 3; }
     tail -1 $O/smoke.log
-    timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
+    timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
     cut -c1-600 $O/bench.json
     ;;
   tests)
@@ -48,7 +48,7 @@ case "$job" in
     done
     ;;
   line)
-    timeout -k 10 600 python bench.py "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
+    timeout -k 10 600 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
     cut -c1-3000 $O/bench.json
     ;;
   prof)

@@ -1,7 +1,9 @@
 import faulthandler
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -21,6 +23,13 @@ ISOLATED_TIMEOUT_S = int(os.environ.get("DLS_ISOLATED_TIMEOUT_S", "300"))
 
 _GPU = None
 
+# The executor tunes every GEMM shape the shipped table (ops/gemm_tuning.json) does not hold —
+# the tests' mini models have many — and persists the choices. A test session persists them
+# into a private copy of the table (DLS_GEMM_TUNING, inherited by the child processes tests
+# start), so running the suite leaves the committed table as it is.
+TUNING_ENV = "DLS_GEMM_TUNING"
+_tuning_dir = None
+
 
 def _has_gpu() -> bool:
     global _GPU
@@ -39,6 +48,19 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "isolated: runs in a fresh child process of its own (see conftest.py)")
     if not faulthandler.is_enabled():
         faulthandler.enable(file=sys.__stderr__, all_threads=True)
+    global _tuning_dir
+    if not os.environ.get(TUNING_ENV):
+        _tuning_dir = tempfile.mkdtemp(prefix="dls_tuning_")
+        shutil.copy(os.path.join(ROOT, "distributed_llm_scheduler_amd", "ops", "gemm_tuning.json"), _tuning_dir)
+        os.environ[TUNING_ENV] = os.path.join(_tuning_dir, "gemm_tuning.json")
+
+
+def pytest_unconfigure(config):
+    global _tuning_dir
+    if _tuning_dir is not None:
+        shutil.rmtree(_tuning_dir, ignore_errors=True)
+        os.environ.pop(TUNING_ENV, None)
+        _tuning_dir = None
 
 
 def pytest_collection_modifyitems(config, items):

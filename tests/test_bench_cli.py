@@ -50,6 +50,47 @@ def test_bench_single_process():
     assert lines[0]["cache_policy"] == {"lm_head": 3, "gemm": 4, "attention_flags": 0}
 
 
+def test_bench_plain_run_is_headline_only_and_full_adds_the_sub_results():
+    """A plain run measures the headline alone; ``--full`` adds the capped / strong sub-results
+    to the same line, whose headline fields keep their meaning."""
+    plain = _run([sys.executable, "bench.py", "--gpus", "1", *ARGS])[0]
+    assert "capped" not in plain and "strong" not in plain and "extras_error" not in plain
+    full = _run([sys.executable, "bench.py", "--gpus", "1", *ARGS, "--full", "--extra-steps", "1"])[0]
+    _check(full, 1)
+    assert full["capped"]["MRU_spec"]["ms_per_step"] > 0 and full["strong"]["ms_per_step"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[k] == full[k]
+    assert plain["value"] == plain["ms_per_step"] and full["value"] == full["ms_per_step"]
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's outputs (the request's logits) as
+    float32 ``.npy`` files; the inputs are seeded, so two runs of the same command write the
+    same arrays, and they are the logits the dense reference computes from those inputs."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        _run([sys.executable, "bench.py", "--gpus", "1", *ARGS, "--dump-outputs", str(tmp_path / d)])
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["output_projection.npy"], files
+        outs.append(np.load(tmp_path / d / files[0]))
+    a, b = outs
+    assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a, b)
+
+    import torch
+    from distributed_llm_scheduler_amd.models import reference
+    from distributed_llm_scheduler_amd.parallel import runtime
+    from distributed_llm_scheduler_amd.parallel.executor import synthetic_tokens
+
+    p = runtime.plan("tiny-gpt2", world=1, scheduler="EFT", seq=32, batch=1, cost_model="bytes")
+    tok = synthetic_tokens("@tokens", 32, p.cfg.vocab_size).view(1, 32)
+    ref = reference.forward(p.cfg, runtime.make_store(p), tok).float().reshape(-1).numpy()
+    assert a.shape == ref.shape
+    assert np.abs(a - ref).max() <= 0.02 * np.abs(ref).max()
+
+
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_gloo():
     lines = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -66,7 +107,7 @@ def test_bench_isolated_device_p2p_subrun_under_torchrun():
     the ONE line, marked isolated."""
     lines = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                   "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", *ARGS,
-                  "--extra-steps", "2", "--device-p2p-extra-cpu"])
+                  "--full", "--extra-steps", "2", "--device-p2p-extra-cpu"])
     assert len(lines) == 1
     _check(lines[0], 2)
     sd = lines[0]["strong_device_p2p"]
@@ -82,7 +123,7 @@ def test_bench_isolated_device_p2p_subrun_crash_keeps_the_headline(monkeypatch):
     monkeypatch.setenv("DLS_TEST_CHILD_ABORT", "1")
     lines = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                   "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", *ARGS,
-                  "--extra-steps", "2", "--device-p2p-extra-cpu", "--extras-timeout", "90"])
+                  "--full", "--extra-steps", "2", "--device-p2p-extra-cpu", "--extras-timeout", "90"])
     assert len(lines) == 1
     _check(lines[0], 2)
     sd = lines[0]["strong_device_p2p"]
@@ -126,10 +167,10 @@ def test_bench_baseline_multi_gpu_configs(world, config):
 
 @pytest.mark.timeout(600)
 def test_bench_extras_two_ranks():
-    """Default extras over 2 gloo ranks: the reference's experiment executed — ONE DAG over the
+    """The ``--full`` extras over 2 gloo ranks: the reference's experiment executed — ONE DAG over the
     two ranks under the 80 % regime with the reference's 60/40 node split (MRU_spec / EFT / DFS,
     real cross-GPU edges), the per-GPU-replica form, and the strong-scaling pipeline run."""
-    lines = _torchrun(2, ["--model", "tiny-gpt2", "--seq", "16", "--steps", "1", "--warmup", "1",
+    lines = _torchrun(2, ["--model", "tiny-gpt2", "--seq", "16", "--steps", "1", "--warmup", "1", "--full",
                           "--extra-steps", "1", "--strong-mb", "4"])
     ln = lines[0]
     cap = ln["capped"]
@@ -199,7 +240,7 @@ def test_bench_extras_watchdog_keeps_headline():
     and the job exits 0 (2 gloo ranks)."""
     lines = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                   "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", *ARGS,
-                  "--extras-timeout", "0.01"])
+                  "--full", "--extras-timeout", "0.01"])
     assert len(lines) == 1
     _check(lines[0], 2)
     assert "unfinished" in lines[0]["extras_error"]
