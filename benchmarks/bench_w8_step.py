@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""One model's step on one GPU under a parameter cap, in bf16 and with fp8 weight storage, the
+two modes alternating on the same device: step time, tasks completed, GB the plan re-fills per
+step and kernel launches of the captured step. One JSON line per run.
+
+    python benchmarks/bench_w8_step.py --model llama3-8b --cap 10.3 [--scheduler EFT] [--rounds 2]
+"""
+from __future__ import annotations
+
+import argparse
+import gc
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
+
+
+def run(model, cap, sched, wd, steps, warmup):
+    dev = torch.device("cuda:0")
+    p = runtime.plan(model, world=1, scheduler=sched, cap_gb=cap, cost_model="bytes", weight_dtype=wd)
+    store = runtime.make_store(p, device_init=runtime.device_init_ok(p, 0))
+    ex = runtime.make_executor(p, 0, dev, store)
+    for _ in range(warmup):
+        ex.step()
+    torch.cuda.synchronize()
+    ex.capture()
+    st = ex.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        st = ex.step()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    out = {"model": model, "weight_dtype": wd, "scheduler": p.scheduler_name, "cap_gb": cap,
+           "param_gb": round(sum(p.param_bytes.values()) / 1e9, 3), "tasks_completed": p.completed,
+           "tasks_total": p.total, "ms_per_step": round(ms, 3),
+           "refill_gb_per_step_planned": round(p.stats["refill_gb_per_step_per_rank"][0], 3),
+           "launches": ex.launches}
+    del ex, store, p
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="llama3-8b")
+    ap.add_argument("--cap", type=float, default=288.0)
+    ap.add_argument("--scheduler", default="EFT")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--modes", default="bf16,fp8")
+    a = ap.parse_args()
+    for _ in range(a.rounds):
+        for wd in a.modes.split(","):
+            print(json.dumps(run(a.model, a.cap, a.scheduler, wd, a.steps, a.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

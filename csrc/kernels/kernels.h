@@ -104,6 +104,36 @@ void launch_gemm_glds_grouped(const GemmArgs& a, int cfg, int n_groups, const in
                               const unsigned long long* w_ptrs, const unsigned long long* c_ptrs, hipStream_t s,
                               const int* a_rows = nullptr);
 
+// W8A16 GEMM (gemm_w8.hip): C = act(alpha * scale[n] * sum_k A[m][k] * Wq[n][k] + bias[n]) + R
+// with Wq stored as OCP e4m3 bytes ([N][ldw], K contiguous) and one fp32 scale per output
+// channel. The fp8 bytes go through LDS, are converted to bf16 in registers (exact) and run on
+// the bf16 MFMA; the scale is applied in the epilogue. K % 16 == 0, any M, N (even for SwiGLU).
+struct GemmW8Args {
+  const void* A;  // bf16 [M][lda]
+  int lda;
+  const void* Wq;  // e4m3 [N][ldw]
+  int ldw;
+  const float* scale;  // fp32 [N], positive
+  void* C;             // bf16 [M][ldc] (SwiGLU: N/2 columns)
+  int ldc;
+  const void* bias;  // bf16 [N] or nullptr
+  const void* R;     // bf16 [M][ldr] or nullptr
+  int ldr;
+  int M, N, K;
+  int act;  // DlsAct
+  float alpha;
+  int config;       // 0..gemm_w8_num_configs()-1
+  int splitk;       // >= 1; > 1: fp32 partial slabs in `workspace`, summed in a fixed order
+  float* workspace;  // gemm_w8_workspace_bytes() when splitk > 1
+  int store_pol;     // output stores: 0 plain, 2 nt, 4 write-through (GemmArgs::stream_pol bits 1, 2)
+};
+int gemm_w8_num_configs();
+void gemm_w8_pick(int M, int N, int K, int* cfg, int* splitk);
+// the largest split of K a config takes for this K (every split covers whole K tiles)
+int gemm_w8_max_splitk(int cfg, int K);
+size_t gemm_w8_workspace_bytes(int M, int N, int splitk);
+void launch_gemm_w8(const GemmW8Args& a, hipStream_t s);
+
 struct AttnArgs {
   const void* q; int ldq;   // bf16, row = token (b*S + s), head h at column h*D
   const void* k; int ldk;   // kv head g at column g*D

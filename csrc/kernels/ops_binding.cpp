@@ -221,6 +221,88 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
   return c;
 }
 
+// W8A16 GEMM (gemm_w8.hip): wq e4m3 [N][K] (K contiguous), scale fp32 [N]. config / splitk: -1 / 0
+// pick by shape. workspace (fp32, optional): the split-K partial slabs — a caller inside a
+// hipGraph capture passes one it allocated before; otherwise the caching allocator provides it.
+at::Tensor gemm_w8(const at::Tensor& a_in, const at::Tensor& wq, const at::Tensor& scale,
+                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& residual, int64_t act,
+                   double alpha, const c10::optional<at::Tensor>& out, int64_t config, int64_t splitk,
+                   int64_t store_pol, const c10::optional<at::Tensor>& workspace) {
+  check_bf16(a_in, "A");
+  at::Tensor a = as2d(a_in);
+  check_rows(a, "A");
+  TORCH_CHECK(wq.is_cuda() && wq.device() == a.device() && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "W must be a float8_e4m3fn tensor on A's GPU");
+  TORCH_CHECK(wq.dim() == 2, "W must be 2-D");
+  const int64_t M = a.size(0), K = a.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K, "W must be [N][K] with K = ", K, ", got ", wq.sizes());
+  TORCH_CHECK(K % 16 == 0, "the fp8-weight GEMM needs K % 16 == 0, got K = ", K);
+  TORCH_CHECK(wq.stride(1) == 1 && wq.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+              "W must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == a.device() && scale.scalar_type() == at::kFloat &&
+                  scale.is_contiguous() && scale.numel() == N,
+              "scale must be a contiguous fp32 [N] tensor on A's GPU");
+  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
+  const bool swiglu = act == kActSwiglu;
+  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
+  const int64_t NO = swiglu ? N / 2 : N;
+  at::Tensor c;
+  if (out.has_value()) {
+    c = as2d(*out);
+    check_bf16(c, "out");
+    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
+                "out must be [M][N_out] with contiguous rows");
+  } else {
+    c = at::empty({M, NO}, a.options());
+  }
+  const void* bptr = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
+    bptr = bias->data_ptr();
+  }
+  const void* rptr = nullptr;
+  int ldr = 0;
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
+    rptr = r.data_ptr();
+    ldr = (int)r.stride(0);
+  }
+  if (M == 0 || N == 0) return c;
+  int cfg = (int)config, sk = (int)splitk;
+  if (cfg < 0 || sk <= 0) {
+    int acfg, ask;
+    gemm_w8_pick((int)M, (int)N, (int)K, &acfg, &ask);
+    if (cfg < 0) {
+      cfg = acfg;
+      if (sk <= 0) sk = ask;
+    } else if (sk <= 0) {
+      sk = 1;
+    }
+  }
+  TORCH_CHECK(cfg < gemm_w8_num_configs(), "unknown fp8-weight GEMM config ", cfg);
+  sk = std::min(sk, gemm_w8_max_splitk(cfg, (int)K));
+  at::Tensor ws;
+  if (sk > 1) {
+    const int64_t need = (int64_t)gemm_w8_workspace_bytes((int)M, (int)N, sk) / 4;
+    if (workspace.has_value()) {
+      ws = *workspace;
+      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
+                      ws.is_contiguous() && ws.numel() >= need,
+                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
+    } else {
+      ws = at::empty({need}, a.options().dtype(at::kFloat));
+    }
+  }
+  GemmW8Args g{a.data_ptr(), (int)a.stride(0), wq.data_ptr(), (int)wq.stride(0), scale.data_ptr<float>(),
+               c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K, (int)act, (float)alpha,
+               cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+  launch_gemm_w8(g, cur_stream());
+  return c;
+}
+
 at::Tensor attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t B, int64_t S,
                      int64_t n_head, int64_t n_kv_head, int64_t head_dim, bool causal, double scale,
                      const c10::optional<at::Tensor>& out, int64_t variant, int64_t Sq, int64_t q_off,
@@ -875,6 +957,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stats_out") = py::none(), py::arg("ext_stats") = py::none(), py::arg("norm_out") = py::none(),
         py::arg("norm_w") = py::none(), py::arg("norm_b") = py::none(), py::arg("norm_mode") = 0,
         py::arg("norm_eps") = 1e-5, py::arg("stream_pol") = 0);
+  m.def("gemm_w8", &gemm_w8, py::arg("a"), py::arg("wq"), py::arg("scale"), py::arg("bias") = py::none(),
+        py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0, py::arg("out") = py::none(),
+        py::arg("config") = -1, py::arg("splitk") = 0, py::arg("store_pol") = 0, py::arg("workspace") = py::none());
+  m.def("gemm_w8_num_configs", &gemm_w8_num_configs);
+  m.def("gemm_w8_pick", [](int M, int N, int K) {
+    int c, s;
+    gemm_w8_pick(M, N, K, &c, &s);
+    return std::make_pair(c, s);
+  });
   m.attr("REGSTAGE") = kRegStage;
   m.attr("PERSIST") = kGemmPersist;
   m.def("gemm_pick_config", &gemm_pick_config);

@@ -18,7 +18,8 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
 
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
---tp, --sp, --seed, --dtype (bf16 only: the kernels compute in bf16 with fp32 accumulation).
+--tp, --sp, --seed, --dtype (bf16: the kernels compute in bf16 with fp32 accumulation),
+--weight-dtype {bf16,fp8} (how GEMM weights are STORED: fp8 = e4m3 + one fp32 scale per output channel).
 """
 from __future__ import annotations
 
@@ -46,7 +47,12 @@ def _common(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--tp", type=int, default=1, help="tensor-parallel shards per layer (DAG transform)")
     ap.add_argument("--sp", type=int, default=1, help="sequence chunks per request (context-parallel DAG transform)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16"],
+                    help="compute dtype of activations and MFMA operands (bf16, fp32 accumulation); the storage of "
+                         "the GEMM weights is selectable with --weight-dtype")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="GEMM weight storage: bf16, or fp8 (OCP e4m3 + one fp32 scale per output channel; dense "
+                         "models, no --tp / --sp): about half the parameter bytes under the same --hbm-cap-gb")
     ap.add_argument("--no-fuse", action="store_true")
 
 
@@ -55,7 +61,11 @@ def _plan(a, world: int, resume: Optional[str] = None):
 
     return runtime.plan(a.model, world=world, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, replicas=a.replicas,
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
-                        placement=a.placement, tp=a.tp, resume=resume, sp=a.sp)
+                        placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype)
+
+
+def _param_gb(p) -> float:
+    return round(sum(p.param_bytes.values()) / 1e9, 6)
 
 
 def cmd_plan(a) -> int:
@@ -63,7 +73,8 @@ def cmd_plan(a) -> int:
 
     t0 = time.time()
     p = _plan(a, a.devices)
-    out = {"model": a.model, "scheduler": p.scheduler_name, "world": p.world, "plan_ms": round((time.time() - t0) * 1e3, 2)}
+    out = {"model": a.model, "scheduler": p.scheduler_name, "world": p.world, "plan_ms": round((time.time() - t0) * 1e3, 2),
+           "weight_dtype": a.weight_dtype, "param_gb": _param_gb(p)}
     out.update(p.stats)
     print(json.dumps(out))
     if a.save:
@@ -201,7 +212,8 @@ def cmd_run(a) -> int:
         print(json.dumps({"model": a.model, "world": world, "scheduler": p.scheduler_name,
                           "tasks_completed": p.stats["tasks_completed"], "tasks_total": p.stats["tasks_total"],
                           "ms_per_step": round(float(t[0].item()), 4), "device": str(dev),
-                          "p2p": getattr(ex.comm, "kind", None), "valid": not invalid}))
+                          "p2p": getattr(ex.comm, "kind", None), "valid": not invalid,
+                          "weight_dtype": a.weight_dtype, "param_gb": _param_gb(p)}))
         if events is not None:
             from .utils.tracing import chrome_trace, kernel_timeline
 
@@ -268,7 +280,7 @@ def cmd_elastic(a) -> int:
     out = run_elastic(world=a.devices, steps=a.steps, fail_rank=a.fail_rank, fail_step=a.fail_step,
                       device=a.device, model=a.model, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb,
                       replicas=a.replicas, batch=a.batch, seq=a.seq, cost_model=a.cost_model, placement=a.placement,
-                      tp=a.tp, sp=a.sp)
+                      tp=a.tp, sp=a.sp, weight_dtype=a.weight_dtype)
     print(json.dumps(out))
     return 0
 

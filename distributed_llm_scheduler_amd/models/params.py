@@ -29,6 +29,9 @@ class TensorSpec:
     std: float = 0.02
     parent: Optional["TensorSpec"] = None  # shard of a larger tensor (tensor parallelism)
     slc: Optional[tuple] = None            # (dim, start, stop) or ("rows", ((a, b), ...))
+    # fp8 weight storage (registry.build weight_dtype="fp8"): a GEMM weight [N, K] kept as e4m3
+    # bytes [N][K] followed (256-B aligned) by one fp32 scale per output channel [N]
+    quant: bool = False
 
     @property
     def numel(self) -> int:
@@ -44,7 +47,41 @@ class ParamGroup:
     tensors: List[TensorSpec] = field(default_factory=list)
 
     def nbytes(self, dtype_bytes: int = 2) -> int:
-        return sum(t.numel for t in self.tensors) * dtype_bytes
+        return sum(t.numel + 4 * t.shape[0] if t.quant else t.numel * dtype_bytes for t in self.tensors)
+
+
+def quant_parts(spec: TensorSpec) -> Tuple[int, int, int]:
+    """A quantised tensor inside its group: (bytes of the e4m3 part, byte offset of the scales
+    from the tensor's start, bytes of the fp32 scales)."""
+    qb = spec.numel
+    return qb, _align(qb), 4 * spec.shape[0]
+
+
+def quantize_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-output-channel e4m3 quantisation with POWER-OF-TWO scales: row n of ``w`` [N, K]
+    becomes ``q[n] = rne(w[n] / scale[n])`` with ``scale[n]`` the smallest 2^e such that
+    ``amax_n / 2^e <= 448`` (an all-zero row: 1). Every e4m3 value times a power of two is a
+    bf16 value, so :func:`dequantize_fp8` of the result is exactly a bf16 tensor. Runs on
+    ``w``'s device. Returns ``(q float8_e4m3fn [N, K], scale fp32 [N])``."""
+    w2 = w.detach().reshape(w.shape[0], -1)
+    N, K = w2.shape
+    q = torch.empty((N, K), dtype=torch.float8_e4m3fn, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    step = max(1, (1 << 26) // max(K, 1))  # rows per pass: the fp32 temporaries stay small
+    for r in range(0, N, step):
+        wf = w2[r:r + step].float()
+        amax = wf.abs().amax(dim=1)
+        m, ex = torch.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+        e = torch.where(m <= 0.875, ex - 9, ex - 8)
+        s = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e), torch.ones_like(amax))
+        scale[r:r + step] = s
+        q[r:r + step] = (wf / s[:, None]).clamp_(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q.reshape(w.shape), scale
+
+
+def dequantize_fp8(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """``q[n][k] * scale[n]`` (exact in bf16 for power-of-two scales)."""
+    return (q.float() * scale.float().reshape(-1, *([1] * (q.dim() - 1)))).to(dtype)
 
 
 def _seed(name: str, base: int) -> int:
@@ -117,6 +154,7 @@ class ParamStore:
         self.pin = (torch.cuda.is_available() and not device_init) if pin is None else pin
         self._host: Dict[str, torch.Tensor] = {}
         self._images: Dict[str, torch.Tensor] = {}
+        self._quant: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}  # quantised name -> (q, scale)
         self._specs: Dict[str, TensorSpec] = {}
         for g in groups.values():
             for sp in g.tensors:
@@ -125,6 +163,8 @@ class ParamStore:
                     sp = sp.parent
 
     def tensor(self, name: str) -> torch.Tensor:
+        """The tensor as the model computes with it: for a quantised name, the DEQUANTISED
+        weight (exactly a bf16 tensor: power-of-two scales)."""
         t = self._host.get(name)
         if t is None:
             spec = self._spec(name)
@@ -132,18 +172,52 @@ class ParamStore:
                 t = _take(self.tensor(spec.parent.name), spec.slc)
             else:
                 t = materialize(spec, self.dtype, "cpu", self.seed)
+            if spec.quant:
+                t = self._quantize(name, t)
             if self.pin:
                 t = t.pin_memory()
             self._host[name] = t
         return t
 
+    def _quantize(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        q, scale = quantize_fp8(t)
+        self._quant[name] = (q.pin_memory(), scale.pin_memory()) if self.pin else (q, scale)
+        return dequantize_fp8(q, scale, self.dtype)
+
+    def quantized(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(q e4m3 [N, K], scale fp32 [N])`` of a quantised tensor (``tensor(name)`` is their
+        product)."""
+        if not self._spec(name).quant:
+            raise KeyError(f"{name} is not stored as fp8")
+        if name not in self._quant:
+            self.tensor(name)
+        return self._quant[name]
+
+    def is_quantized(self, name: str) -> bool:
+        sp = self._specs.get(name)
+        return sp is not None and sp.quant
+
     def _spec(self, name: str) -> TensorSpec:
         return self._specs[name]
 
-    def fill(self, name: str, out: torch.Tensor) -> None:
-        """Write tensor ``name`` into ``out`` (an HBM arena view)."""
-        if self.device_init and out.is_cuda and name not in self._host:
-            fill_on_device(self._spec(name), out, self.seed)
+    def fill(self, name: str, out: torch.Tensor, scale_out: Optional[torch.Tensor] = None) -> None:
+        """Write tensor ``name`` into ``out`` (an HBM arena view); a quantised tensor's e4m3
+        part into ``out`` and its scales into ``scale_out``."""
+        spec = self._spec(name)
+        if spec.quant:
+            if self.device_init and out.is_cuda and name not in self._host:
+                # bf16 scratch in HBM, quantised there: still no host copy
+                full = torch.empty(spec.shape, dtype=self.dtype, device=out.device)
+                fill_on_device(spec, full, self.seed)
+                q, scale = quantize_fp8(full)
+                out.copy_(q)
+                scale_out.copy_(scale)
+            else:
+                q, scale = self.quantized(name)
+                out.copy_(q, non_blocking=True)
+                scale_out.copy_(scale, non_blocking=True)
+        elif self.device_init and out.is_cuda and name not in self._host:
+            fill_on_device(spec, out, self.seed)
         else:
             out.copy_(self.tensor(name), non_blocking=True)
 
@@ -158,6 +232,12 @@ class ParamStore:
             total, layout = group_layout(self.groups[pid], torch.tensor([], dtype=self.dtype).element_size())
             img = torch.zeros(total, dtype=torch.uint8)
             for spec, off in layout:
+                if spec.quant:
+                    q, scale = self.quantized(spec.name)
+                    qb, s_off, sb = quant_parts(spec)
+                    img[off:off + qb].copy_(q.contiguous().view(-1).view(torch.uint8))
+                    img[off + s_off:off + s_off + sb].copy_(scale.contiguous().view(torch.uint8))
+                    continue
                 t = self.tensor(spec.name).contiguous()
                 img[off:off + t.numel() * t.element_size()].copy_(t.view(-1).view(torch.uint8))
             if self.pin:
@@ -178,6 +258,8 @@ class ParamStore:
         if tuple(value.shape) != tuple(spec.shape):
             raise ValueError(f"{name}: expected shape {spec.shape}, got {tuple(value.shape)}")
         t = value.detach().to("cpu", self.dtype).contiguous()
+        if spec.quant:  # stored as fp8: what tensor() returns is what the kernels multiply
+            t = self._quantize(name, t)
         self._host[name] = t.pin_memory() if self.pin else t
         self._images = {k: v for k, v in self._images.items()
                         if all(sp.name != name for sp in self.groups[k].tensors)}
@@ -186,12 +268,21 @@ class ParamStore:
 GROUP_ALIGN = 256
 
 
+def _align(n: int) -> int:
+    return (n + GROUP_ALIGN - 1) // GROUP_ALIGN * GROUP_ALIGN
+
+
 def group_layout(group: ParamGroup, dtype_bytes: int = 2):
     """Byte layout of a parameter group inside the HBM parameter arena: every tensor
-    starts 256-B aligned (16-B vector loads, cache-line aligned rows).
+    starts 256-B aligned (16-B vector loads, cache-line aligned rows). A quantised tensor
+    (``spec.quant``) takes N*K bytes of e4m3 and, 256-B aligned behind them, 4*N bytes of
+    scales (:func:`quant_parts`).
     Returns ``(total_bytes, [(spec, byte_offset), ...])``."""
     off, out = 0, []
     for spec in group.tensors:
         out.append((spec, off))
-        off += (spec.numel * dtype_bytes + GROUP_ALIGN - 1) // GROUP_ALIGN * GROUP_ALIGN
+        if spec.quant:
+            off += _align(spec.numel) + _align(4 * spec.shape[0])
+        else:
+            off += _align(spec.numel * dtype_bytes)
     return off, out

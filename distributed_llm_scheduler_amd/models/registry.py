@@ -29,12 +29,47 @@ def build_dag(cfg: ModelConfig, batch: int = 1, seq: int = 512, cost_model: str 
     raise KeyError(cfg.family)
 
 
+WEIGHT_DTYPES = ("bf16", "fp8")
+# (op kind, weight key) pairs that read a tensor as a GEMM weight operand
+_GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("attention", "w_o"),
+                  ("swiglu_mlp", "w_gate_up"), ("swiglu_mlp", "w_down")}
+
+
+def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup]) -> List[str]:
+    """Mark for fp8 storage (``TensorSpec.quant``) every tensor that EVERY reader reads as a
+    GEMM weight operand. Embedding tables, norm gains, biases and a weight an embedding also
+    gathers from (GPT-2's tied ``wte``) stay bf16. Returns the marked names."""
+    gemm, other = set(), set()
+    for t in tasks:
+        if t.op is None:
+            continue
+        for key, name in t.op.weights.items():
+            if isinstance(name, str):
+                (gemm if (t.op.kind, key) in _GEMM_OPERANDS else other).add(name)
+    marked = []
+    for g in groups.values():
+        for sp in g.tensors:
+            if sp.name in gemm and sp.name not in other and len(sp.shape) == 2 and sp.parent is None:
+                sp.quant = True
+                marked.append(sp.name)
+    return marked
+
+
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
-          tp: int = 1, sp: int = 1) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          tp: int = 1, sp: int = 1, weight_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
-    node into sequence chunks (models/transforms.py)."""
+    node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
+    of a dense model are stored as e4m3 with one fp32 scale per output channel
+    (:func:`mark_fp8`); not with MoE models, ``tp`` or ``sp``."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     cfg = get_config(model)
+    if weight_dtype == "fp8":
+        if cfg.n_experts:
+            raise ValueError("weight_dtype='fp8' does not cover MoE models (the grouped expert GEMM is bf16)")
+        if tp > 1 or sp > 1:
+            raise ValueError("weight_dtype='fp8' does not combine with tensor or sequence parallelism (tp, sp > 1)")
     tasks: List[Task] = []
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
@@ -47,4 +82,6 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
             raise ValueError("combine sequence and tensor parallelism through separate DAGs (not both)")
         from .transforms import sequence_parallel
         tasks, groups = sequence_parallel(tasks, groups, cfg, sp)
+    if weight_dtype == "fp8":
+        mark_fp8(tasks, groups)
     return tasks, groups, cfg

@@ -312,6 +312,66 @@ def linear(x, w, bias=None, act=None, residual=None, alpha=1.0, out=None, rows=N
     return y
 
 
+def quantize_fp8(w):
+    """bf16 GEMM weight [N, K] -> ``(q, scale)``: OCP e4m3 (``torch.float8_e4m3fn``, K
+    contiguous) and one fp32 POWER-OF-TWO scale per output channel, the smallest 2^e with
+    ``amax_n / 2^e <= 448`` (an all-zero row: 1); round-to-nearest, saturating at +-448, no NaN
+    code. ``W[n][k] ~= q[n][k] * scale[n]``, and that product is exactly a bf16 value. Runs on
+    ``w``'s device."""
+    from ..models.params import quantize_fp8 as _q
+    return _q(w)
+
+
+def dequantize_fp8(q, scale, dtype=torch.bfloat16):
+    """``q[n][k] * scale[n]`` as ``dtype`` (exact in bf16 for power-of-two scales)."""
+    from ..models.params import dequantize_fp8 as _d
+    return _d(q, scale, dtype)
+
+
+W8_SPLITS = (1, 2, 4, 8)  # split-K factors of the fp8-weight GEMM (csrc/kernels/gemm_w8.hip)
+
+
+def w8_configs() -> int:
+    """Number of tile configurations of the fp8-weight GEMM (``linear_w8(config=...)``)."""
+    return int(ext().gemm_w8_num_configs())
+
+
+def w8_workspace_elems(M: int, N: int, K: int) -> int:
+    """fp32 elements of split-K workspace the shape's automatic config needs (0: no K split)."""
+    _, sk = ext().gemm_w8_pick(int(M), int(N), int(K))
+    return int(sk) * int(M) * int(N) if sk > 1 else 0
+
+
+def linear_w8(x, q, scale, bias=None, act=None, residual=None, alpha=1.0, out=None, config=None, workspace=None):
+    """``act(alpha * scale[n] * sum_k x[m][k] * q[n][k] + bias[n]) + residual`` with an fp8
+    weight: ``q`` e4m3 [N, K] (K contiguous, K % 16 == 0), ``scale`` fp32 [N] (any positive
+    values), fp32 accumulation, bf16 output. GPU: one HIP kernel (gemm_w8.hip: the fp8 bytes go
+    through LDS, are converted to bf16 in registers and multiplied on the bf16 MFMA; the scale
+    is applied in the epilogue). ``act="swiglu"``: the rows of ``q`` and ``scale`` interleave
+    gate and up in blocks of ``SWIGLU_BLOCK`` (:func:`interleave_gate_up`), N/2 outputs.
+    ``config``: ``None`` picks by shape; ``c`` forces tile configuration c (< :func:`w8_configs`)
+    without a K split; ``(c, s)`` also splits K s ways (partial sums in fp32, reduced in a fixed
+    order: bitwise reproducible). ``workspace`` (fp32, GPU): the split-K partial slabs, for
+    callers that must not allocate (hipGraph capture). CPU tensors run :func:`ref_linear` on
+    the dequantised weight."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if q.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"linear_w8: the weight must be float8_e4m3fn, got {q.dtype}")
+    if _gpu(x):
+        n_out = q.shape[0] // 2 if a == SWIGLU else q.shape[0]
+        cfg, sk = (-1, 0) if config is None else (tuple(config) if isinstance(config, (tuple, list)) else (config, 1))
+        y = ext().gemm_w8(x, q, scale, bias, residual, a, float(alpha), out, int(cfg), int(sk),
+                          _stream_pol(q.shape[0], q.shape[1]) & 6, workspace)
+        return y.view(x.shape[:-1] + (n_out,)) if out is None else out
+    if x.shape[-1] % 16:
+        raise ValueError(f"linear_w8: K must be a multiple of 16, got {x.shape[-1]}")
+    y = ref_linear(x, dequantize_fp8(q, scale, torch.float32), bias, act, residual, alpha)
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
 def derive_norm_gemm(w, ln_w, ln_b=None, bias=None):
     """Fold a norm's affine into the following GEMM: returns (W' = W * ln_w, colsum(W') in
     fp32, bias' = bias + W @ ln_b). W' is rounded to bf16 BEFORE the column sums, so the

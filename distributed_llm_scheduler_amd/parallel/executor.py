@@ -40,7 +40,7 @@ import torch
 from .. import ops
 from ..core.task import Task
 from ..ops import tuning as _tuning
-from ..models.params import ParamStore, group_layout
+from ..models.params import ParamStore, group_layout, quant_parts
 from ..utils.tracing import Roctx
 from . import lifetime
 from .comm import make_comm
@@ -126,6 +126,7 @@ FOLD_MAX_K = 1024  # fold a preceding norm into the GEMM only up to this K (see 
 # widest norm input whose statistics a producer GEMM hands over (beyond it: a norm kernel)
 HANDOFF_MAX_K = int(os.environ.get("DLS_HANDOFF_MAX_K", str(FOLD_MAX_K)))
 GUARD_BYTES, GUARD_VALUE = 4096, 0xA5  # debug-mode canary after each arena slab
+SCALE_SUFFIX = "@scale"  # view name of an fp8 weight's per-row fp32 scales (DAGExecutor._views_at)
 # producer GEMMs emit row statistics for the next folded norm (GPU); DLS_STATS_HANDOFF=0 disables
 STATS_HANDOFF = os.environ.get("DLS_STATS_HANDOFF", "1") != "0"
 # the embedding kernel hands layer 0's folded norm its rows' statistics too (0: that norm's GEMM
@@ -225,6 +226,11 @@ class DAGExecutor:
                 for v in set(x for x in t.op.weights.values() if isinstance(x, str)):
                     kinds.setdefault(v, set()).add(t.op.kind)
         self._w_users: Dict[str, int] = {v: len(k) for v, k in kinds.items()}
+        # fp8 weight storage (registry.mark_fp8): tensors held as e4m3 + per-row fp32 scales.
+        # Their GEMMs run ops.linear_w8 with the norm as its own kernel: no folded norm, no row
+        # statistics, no post-norm, RoPE stand-alone, none of the one-launch fused blocks.
+        self._q_names = {sp.name for g in store.groups.values() for sp in g.tensors if sp.quant}
+        self._w8_ws: Optional[torch.Tensor] = None  # split-K partial slabs of the fp8-weight GEMMs
         # GPU, host-image refills: a transformed weight's bytes are written back into a private
         # copy of its group's pinned image, so every later refill restores the TRANSFORMED
         # weight and its (colsum, bias') stay valid wherever the group lands (no re-derivation
@@ -378,6 +384,8 @@ class DAGExecutor:
             P, Q = ins[i], ins[j]
             if any(ins[k].op not in ("load", "evict") for k in range(i + 1, j)):
                 continue
+            if self._w8_group(P.group) or self._w8_group(Q.group):
+                continue  # fp8 weights: the norm stays its own kernel on both backends
             pg = [self.tasks[t] for t in P.group]
             qg = [self.tasks[t] for t in Q.group]
             N = qg[0]
@@ -578,6 +586,8 @@ class DAGExecutor:
             if b.op != "run" or b.kind != "linear+residual":
                 continue
             g1, g2 = [self.tasks[t] for t in a.group], [self.tasks[t] for t in b.group]
+            if self._w8_group(a.group) or self._w8_group(b.group):
+                continue  # fp8 weights never take the one-launch block
             if g2[0].dependencies != [a.task] or b.wait_sends or j in self._post_norm \
                     or self._ext_stats.get(g1[0].op.inputs[0]) is None:
                 continue
@@ -692,6 +702,8 @@ class DAGExecutor:
         producers = {ins.task: ins for ins in self.prog.instrs if ins.op == "run"}
 
         def emits(ins) -> bool:
+            if self._w8_group(ins.group):
+                return False  # the fp8-weight GEMM emits no row statistics
             grp = [self.tasks[t] for t in ins.group]
             lead_norm = grp[0].op.kind in ("layernorm", "rmsnorm") and len(grp) > 1
             head = grp[1] if lead_norm else grp[0]
@@ -707,7 +719,7 @@ class DAGExecutor:
             if ins.op != "run":
                 continue
             grp = [self.tasks[t] for t in ins.group]
-            if len(grp) > 1 and grp[0].op.kind in ("layernorm", "rmsnorm"):
+            if len(grp) > 1 and grp[0].op.kind in ("layernorm", "rmsnorm") and not self._w8_group(ins.group):
                 src = grp[0].op.inputs[0]
                 pi = producers.get(src)
                 # measured (MI355X, scripts/gpu_ab.sh): a win where the norm would otherwise be
@@ -751,6 +763,8 @@ class DAGExecutor:
             spec = {s.name: s for pid in t.params_needed for s in g[pid].tensors}
             names = [(k, v) for k, v in op.weights.items() if k.startswith("w") and isinstance(v, str)]
             for wk, n in names:
+                if n in spec and spec[n].quant:
+                    continue  # the fp8-weight GEMM picks by shape: no tuned table
                 if n in spec and len(spec[n].shape) == 2 and op.kind not in ("embedding", "layernorm", "rmsnorm"):
                     N, K = spec[n].shape
                     if op.kind == "moe_expert":
@@ -806,8 +820,27 @@ class DAGExecutor:
         views = {}
         for spec, sub in layout:
             n = spec.numel
+            if spec.quant:  # e4m3 bytes, then (256-B aligned) one fp32 scale per row
+                qb, s_off, sb = quant_parts(spec)
+                b = off + sub
+                views[spec.name] = self.param_slab[b:b + qb].view(torch.float8_e4m3fn).view(spec.shape)
+                views[spec.name + SCALE_SUFFIX] = self.param_slab[b + s_off:b + s_off + sb].view(torch.float32)
+                continue
             views[spec.name] = self.param_slab[off + sub:off + sub + 2 * n].view(self.dtype).view(spec.shape)
         return off, total, layout, views
+
+    def _w8_group(self, ids) -> bool:
+        """Does this fused group read a weight stored as fp8?"""
+        if not self._q_names:
+            return False
+        return any(isinstance(v, str) and v in self._q_names
+                   for t in ids if self.tasks[t].op is not None for v in self.tasks[t].op.weights.values())
+
+    def _store_fill(self, spec, views) -> None:
+        if spec.quant:
+            self.store.fill(spec.name, views[spec.name], views[spec.name + SCALE_SUFFIX])
+        else:
+            self.store.fill(spec.name, views[spec.name])
 
     def _map(self, pid: str, off: int, total: int, views) -> None:
         """Point the group's tensor names at its views in the arena region [off, off+total)."""
@@ -925,7 +958,7 @@ class DAGExecutor:
                 self.param_slab[off:off + total].copy_(img, non_blocking=True)
         else:
             if rec is not None and not self.gpu:  # CPU runner: a callback fill
-                rec.r.add_pycall(lambda: [self.store.fill(sp.name, views[sp.name]) for sp, _ in layout])
+                rec.r.add_pycall(lambda: [self._store_fill(sp, views) for sp, _ in layout])
                 self._valid.append((off, total, pid))
                 stats.param_fills += 1
                 stats.bytes_filled += total
@@ -933,7 +966,7 @@ class DAGExecutor:
             if rec is not None:
                 raise RuntimeError("step runner: a parameter refill without a host image cannot be recorded")
             for spec, _ in layout:
-                self.store.fill(spec.name, views[spec.name])
+                self._store_fill(spec, views)
         self._valid.append((off, total, pid))
         stats.param_fills += 1
         stats.bytes_filled += total
@@ -1093,7 +1126,8 @@ class DAGExecutor:
                                   or any(i.op == "load" and i.peer >= 0 for i in self.prog.instrs))
         return self._refills_memo
 
-    def _persist_transform(self, w_name: str, W: torch.Tensor, d: tuple) -> None:
+    def _persist_transform(self, w_name: str, W: torch.Tensor, d: tuple,
+                           scale: Optional[torch.Tensor] = None) -> None:
         """Write the transformed weight into a private copy of its group's host image (pinned
         on GPU; once, in an eager step). Every later refill — from the host image, or from a
         peer that holds the group in the same form — then carries the transformed bytes."""
@@ -1115,6 +1149,9 @@ class DAGExecutor:
             self._img_override[pid] = img
         nb = W.numel() * W.element_size()
         img[sub:sub + nb].copy_(W.reshape(-1).view(torch.uint8))  # blocking D2H
+        if scale is not None:  # an fp8 weight: its per-row scales moved with the rows
+            _, s_off, sb = quant_parts(self.store._spec(w_name))
+            img[sub + s_off:sub + s_off + sb].copy_(scale.view(torch.uint8))
         self._derived_named[w_name] = d
 
     def _gemm(self, x, w_name, b_name, norm: Optional[Task], act=None, residual=None, out=None, rope=None,
@@ -1125,6 +1162,25 @@ class DAGExecutor:
         ``act="swiglu"``: W is a [gate; up] weight, interleaved on first use. ``rope`` /
         ``rope_perm``: RoPE in the epilogue over pair-interleaved q/k rows."""
         sw = act == "swiglu"
+        if w_name in self._q_names:
+            # fp8 weight: the norm as its own kernel (folding W * gain would break the per-row
+            # scale), the fp8-weight GEMM, then RoPE stand-alone on the natural q/k layout
+            if stats_out is not None:
+                raise RuntimeError(f"{w_name}: an fp8-weight GEMM emits no row statistics")
+            if norm is not None:
+                xn = self._scratch("norm", x.shape)
+                if norm.op.kind == "layernorm":
+                    ops.layernorm(x, self._w(norm.op.weights["w"]), self._w(norm.op.weights["b"]),
+                                  norm.op.attrs.get("eps", 1e-5), out=xn)
+                else:
+                    ops.rmsnorm(x, self._w(norm.op.weights["w"]), norm.op.attrs.get("eps", 1e-5), out=xn)
+                x = xn
+            y = self._linear(x, w_name, b_name, act=act, residual=residual, out=out, interleave=sw)
+            if rope is not None:
+                cos, sin, S, D, cols = rope
+                nh, nkv, _ = rope_perm
+                ops.rope_(y, S, nh, nkv, D, nh * D, cos, sin)
+            return y
         ext = self._ext_stats.get(norm.op.inputs[0]) if norm is not None else None
         shared = self._w_users.get(w_name, 1) > 1
         if norm is not None and self.gpu and (ext is not None or x.shape[-1] <= FOLD_MAX_K) \
@@ -1158,6 +1214,50 @@ class DAGExecutor:
                 # with a replica whose input came from a peer without row statistics)
                 raise RuntimeError(f"{w_name}: unfolded GEMM over a weight another reader transformed in place")
         return ops.linear(x, W, bias, act=act, residual=residual, out=out, rope=rope, stats_out=stats_out)
+
+    def _linear(self, x, w_name, b_name=None, act=None, residual=None, out=None, stats_out=None, post_norm=None,
+                interleave: bool = False):
+        """A plain GEMM node on a resident weight, by the weight's storage: bf16 ->
+        ``ops.linear``; fp8 -> ``ops.linear_w8`` (no row statistics, no post-norm: the planners
+        give such groups neither)."""
+        W = self._w(w_name)
+        bias = self._w(b_name) if b_name else None
+        if W.dtype != torch.float8_e4m3fn:
+            return ops.linear(x, W, bias, act=act, residual=residual, out=out, stats_out=stats_out,
+                              post_norm=post_norm)
+        if stats_out is not None or post_norm is not None:
+            raise RuntimeError(f"{w_name}: an fp8-weight GEMM takes no row statistics / post-norm")
+        scale = self._w(w_name + SCALE_SUFFIX)
+        if interleave:
+            bias = self._prep_w8(w_name, W, scale, bias)
+        ws = None
+        if self.gpu:
+            # split-K partial slabs: one buffer per rank, grown in eager steps only (kernels of
+            # one rank run in order on its stream, so consecutive GEMMs may share it)
+            need = ops.w8_workspace_elems(x.numel() // x.shape[-1], W.shape[0], W.shape[1])
+            if need and (self._w8_ws is None or self._w8_ws.numel() < need):
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("fp8-weight GEMM workspace must be allocated before hipGraph capture")
+                self._w8_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            ws = self._w8_ws if need else None
+        return ops.linear_w8(x, W, scale, bias, act=act, residual=residual, out=out, workspace=ws)
+
+    def _prep_w8(self, w_name: str, q: torch.Tensor, scale: torch.Tensor, bias):
+        """SwiGLU row interleave of an fp8 [gate; up] weight, IN PLACE once per fill: the e4m3
+        rows and their scales together (and the bias with them). Persisted into the group's
+        host image like a bf16 transform, so refills carry the interleaved bytes."""
+        named = self._derived_named.get(w_name)
+        if named is not None:
+            return named[1]
+        key = (w_name, q.data_ptr())
+        d = self._derived_cache.get(key)
+        if d is None:
+            q.view(torch.uint8).copy_(ops.interleave_gate_up(q.view(torch.uint8)))
+            scale.copy_(ops.interleave_gate_up(scale))
+            d = (None, ops.interleave_gate_up(bias) if bias is not None else None)
+            self._derived_cache[key] = d
+            self._persist_transform(w_name, q, d, scale=scale)
+        return d[1]
 
     def _scratch(self, tag: str, shape) -> torch.Tensor:
         """Reusable per-rank buffer (allocated on first use, i.e. in an eager warm-up step,
@@ -1264,7 +1364,7 @@ class DAGExecutor:
         if self._ext_stats.get(norm.op.inputs[0]) is None or x.shape[-1] > FOLD_MAX_K \
                 or self._pn_given == norm.id or self._pn is not None:
             return False
-        if self._w_users.get(W["w_qkv"], 1) > 1:
+        if self._w_users.get(W["w_qkv"], 1) > 1 or W["w_qkv"] in self._q_names or W["w_o"] in self._q_names:
             return False
         return ops.attn_block_ok(x.shape[0], x.shape[-1], B, S, a["n_head"], a["n_kv_head"], a["head_dim"])
 
@@ -1349,8 +1449,8 @@ class DAGExecutor:
                 self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv)
             ops.attention(qkv[:, :nh * D], qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], B, S, nh, nkv,
                           D, causal=a.get("causal", True), out=o)
-            ops.linear(o, self._w(W["w_o"]), self._w(W["b_o"]) if "b_o" in W else None, residual=residual,
-                       out=self._flat(out), stats_out=st_out, post_norm=self._post_norm_out(self._flat(out)))
+            self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
+                         post_norm=self._post_norm_out(self._flat(out)))
         elif k == "qkv_proj":
             # sequence chunk c's QKV rows (RoPE at its absolute positions c*Sc ..)
             x = self._flat(self._x(src))
@@ -1388,8 +1488,8 @@ class DAGExecutor:
             M, F = x.shape[0], a["ffn"]
             h = self._ws(0, (M, F))
             self._gemm(x, W["w_gate_up"], None, norm, act="swiglu", out=h)  # SwiGLU in the epilogue
-            ops.linear(h, self._w(W["w_down"]), residual=residual, out=self._flat(out), stats_out=st_out,
-                       post_norm=self._post_norm_out(self._flat(out)))
+            self._linear(h, W["w_down"], residual=residual, out=self._flat(out), stats_out=st_out,
+                         post_norm=self._post_norm_out(self._flat(out)))
         elif k == "moe_expert":
             self._moe_expert(head, self._flat(out))
         elif k == "moe_combine":

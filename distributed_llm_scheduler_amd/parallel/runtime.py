@@ -66,7 +66,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          batch: int = 1, seq: int = 512, cost_model: str = "bytes", fuse: bool = True,
          node_speeds: Optional[Sequence[float]] = None, link_bw_gbps: float = 153.0,
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
-         residency: Optional[str] = None, merge_mb: int = 1) -> Plan:
+         residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16") -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -100,6 +100,11 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     request keeps its own token ids and its own rows of the merged outputs
     (``Plan.requests``, ``DAGExecutor.output("r{k}/...")``).
 
+    ``weight_dtype="fp8"``: the GEMM weights of a dense model are stored (and budgeted, filled
+    and multiplied) as e4m3 bytes with one fp32 scale per output channel (registry.mark_fp8):
+    about half the parameter bytes under the same cap. Raises ``ValueError`` with an MoE model,
+    ``tp > 1`` or ``sp > 1``.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -114,6 +119,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                 link_bw_gbps=link_bw_gbps, placement=placement, tp=tp)
     if sp > 1:
         args["sp"] = sp
+    if weight_dtype != "bf16":  # (only when not the default: plans saved before it still resume)
+        args["weight_dtype"] = weight_dtype
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -128,7 +135,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
             for j, k in enumerate(members):
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
-                                        sp=sp)
+                                        sp=sp, weight_dtype=weight_dtype)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
     nodes = [Node(f"gpu{r}", caps_gb[r], (node_speeds[r] if node_speeds else 1.0), device=r) for r in range(world)]
     node_rank = {n.id: r for r, n in enumerate(nodes)}
@@ -240,6 +247,8 @@ def _resume(path: str, args: Dict, sched):
         raise ValueError(f"{path}: not a saved plan")
     saved = dict(doc["args"])
     mismatch = {k: (saved.get(k), v) for k, v in args.items() if k not in ("fuse",) and saved.get(k) != v}
+    if saved.get("weight_dtype", "bf16") != args.get("weight_dtype", "bf16"):  # (absent: the default)
+        mismatch["weight_dtype"] = (saved.get("weight_dtype", "bf16"), args.get("weight_dtype", "bf16"))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
