@@ -4,6 +4,9 @@ two modes alternating on the same device: step time, tasks completed, GB the pla
 step and kernel launches of the captured step. One JSON line per run.
 
     python benchmarks/bench_w8_step.py --model llama3-8b --cap 10.3 [--scheduler EFT] [--rounds 2]
+    python benchmarks/bench_w8_step.py --model mixtral-8x7b --weight-dtype fp8-experts [--cap 65.4]
+
+``--weight-dtype D`` runs bf16 next to D (``--modes`` lists the modes explicitly).
 """
 from __future__ import annotations
 
@@ -55,8 +58,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--modes", default="bf16,fp8")
+    ap.add_argument("--weight-dtype", default="fp8", choices=["fp8", "fp8-experts"],
+                    help="the fp8 mode measured next to bf16 (fp8-experts: the MoE models)")
+    ap.add_argument("--modes", default=None, help="comma-separated weight dtypes (default: bf16,<--weight-dtype>)")
     a = ap.parse_args()
+    if a.modes is None:
+        a.modes = "bf16," + a.weight_dtype
     for _ in range(a.rounds):
         for wd in a.modes.split(","):
             print(json.dumps(run(a.model, a.cap, a.scheduler, wd, a.steps, a.warmup)), flush=True)

@@ -134,6 +134,37 @@ int gemm_w8_max_splitk(int cfg, int K);
 size_t gemm_w8_workspace_bytes(int M, int N, int splitk);
 void launch_gemm_w8(const GemmW8Args& a, hipStream_t s);
 
+// Grouped W8A16 GEMM (gemm_w8_grouped.hip): the contract of launch_gemm_glds_grouped with the
+// arithmetic of launch_gemm_w8. n_groups groups in ONE launch; group g multiplies rows
+// [offsets[g], offsets[g+1]) — row r of A, or token row a_rows[r] of A — by its e4m3 weight
+// w_ptrs[g] ([N][K], K contiguous) with channel scales s_ptrs[g] (fp32 [N]) and writes them at
+// the same rows of C (c_ptrs == nullptr) or compactly to rows 0..min(count, compact_rows)-1 of
+// c_ptrs[g] ([.][ldc]). act: ACT_NONE or ACT_SWIGLU (rows and scales interleaved in blocks of
+// 16, N/2 outputs, N % 32 == 0). K % 16 == 0, any N, any counts (zero included). No split-K,
+// no atomics, no host sync.
+struct GemmW8GroupedArgs {
+  const void* A;  // bf16 [.][lda]
+  int lda;
+  const int* a_rows;  // device int32 [R] or nullptr
+  const int* offsets;  // device int32 [n_groups + 1]
+  const unsigned long long* w_ptrs;  // device [n_groups]
+  const unsigned long long* s_ptrs;  // device [n_groups]
+  const unsigned long long* c_ptrs;  // device [n_groups] or nullptr
+  void* C;                           // bf16 [R][ldc] when c_ptrs == nullptr
+  int ldc;
+  int compact_rows;
+  int R, N, K;  // R: rows all groups cover together (offsets are clamped to it)
+  int act;
+  int n_groups;
+  int config;          // 0..gemm_w8_grouped_num_configs()-1
+  int shared_weights;  // groups repeat weights, same-weight groups adjacent: they run side by side
+  int store_pol;       // as GemmW8Args::store_pol
+};
+int gemm_w8_grouped_num_configs();
+int gemm_w8_grouped_tile_rows(int cfg);  // row-tile height of a config
+int gemm_w8_grouped_pick(int rows_hint, int N, int K, int n_groups);
+void launch_gemm_w8_grouped(const GemmW8GroupedArgs& a, hipStream_t s);
+
 struct AttnArgs {
   const void* q; int ldq;   // bf16, row = token (b*S + s), head h at column h*D
   const void* k; int ldk;   // kv head g at column g*D

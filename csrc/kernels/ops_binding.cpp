@@ -786,6 +786,91 @@ void gemm_grouped(const at::Tensor& x, const std::vector<at::Tensor>& weights, c
                            arp);
 }
 
+// gemm_grouped with fp8 expert weights (gemm_w8_grouped.hip): weights E x e4m3 [N][K], scales
+// E x fp32 [N]; w_ptrs / s_ptrs / out_ptrs: int64 [E] device tensors of their addresses (cached
+// by the caller: hipGraph-safe). config < 0: picked by (rows_hint, N, K).
+void gemm_grouped_w8(const at::Tensor& x, const std::vector<at::Tensor>& weights,
+                     const std::vector<at::Tensor>& scales, const at::Tensor& w_ptrs, const at::Tensor& s_ptrs,
+                     const at::Tensor& offsets, int64_t act, const c10::optional<at::Tensor>& out,
+                     const std::vector<at::Tensor>& outs, const c10::optional<at::Tensor>& out_ptrs, int64_t config,
+                     int64_t rows_hint, const c10::optional<at::Tensor>& a_rows, bool shared_weights,
+                     int64_t store_pol) {
+  const int64_t E = (int64_t)weights.size();
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  TORCH_CHECK(E > 0 && (int64_t)scales.size() == E, "one scale tensor per expert weight");
+  const int* arp = nullptr;
+  if (a_rows.has_value()) {
+    TORCH_CHECK(a_rows->is_cuda() && a_rows->scalar_type() == at::kInt && a_rows->is_contiguous(),
+                "a_rows: contiguous int32 on the GPU");
+    arp = a_rows->data_ptr<int32_t>();
+  }
+  const int64_t R = a_rows.has_value() ? a_rows->numel() : x.size(0), K = x.size(1), N = weights[0].size(0);
+  TORCH_CHECK(act == 0 || act == kActSwiglu, "grouped fp8-weight GEMM: act is none or SwiGLU");
+  const bool sw = act == kActSwiglu;
+  const int64_t NO = sw ? N / 2 : N;
+  TORCH_CHECK(K >= 16 && K % 16 == 0, "the fp8-weight GEMM needs K % 16 == 0, got K = ", K);
+  for (int64_t e = 0; e < E; ++e) {
+    const auto& w = weights[e];
+    const auto& sc = scales[e];
+    TORCH_CHECK(w.is_cuda() && w.device() == x.device() && w.scalar_type() == at::kFloat8_e4m3fn,
+                "expert weights must be float8_e4m3fn tensors on x's GPU");
+    TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == N && w.size(1) == K &&
+                    reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                "expert weights: contiguous, 16-byte aligned [N][K]");
+    TORCH_CHECK(sc.is_cuda() && sc.device() == x.device() && sc.scalar_type() == at::kFloat && sc.is_contiguous() &&
+                    sc.numel() == N,
+                "expert scales: contiguous fp32 [N] on x's GPU");
+  }
+  TORCH_CHECK(w_ptrs.is_cuda() && w_ptrs.scalar_type() == at::kLong && w_ptrs.numel() == E, "w_ptrs int64 [E]");
+  TORCH_CHECK(s_ptrs.is_cuda() && s_ptrs.scalar_type() == at::kLong && s_ptrs.numel() == E, "s_ptrs int64 [E]");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kInt && offsets.numel() == E + 1,
+              "offsets int32 [E+1]");
+  TORCH_CHECK(!sw || N % 32 == 0, "SwiGLU needs interleaved gate/up rows (N % 32 == 0)");
+  int cfg = (int)config;
+  if (cfg < 0) cfg = gemm_w8_grouped_pick((int)(rows_hint > 0 ? rows_hint : std::max<int64_t>(1, R / E)), (int)N, (int)K,
+                                          (int)E);
+  TORCH_CHECK(cfg < gemm_w8_grouped_num_configs(), "unknown grouped fp8-weight GEMM config ", cfg);
+  GemmW8GroupedArgs g{};
+  g.A = x.data_ptr();
+  g.lda = (int)x.stride(0);
+  g.a_rows = arp;
+  g.offsets = offsets.data_ptr<int32_t>();
+  g.w_ptrs = reinterpret_cast<const unsigned long long*>(w_ptrs.data_ptr<int64_t>());
+  g.s_ptrs = reinterpret_cast<const unsigned long long*>(s_ptrs.data_ptr<int64_t>());
+  g.R = (int)R;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.act = (int)act;
+  g.n_groups = (int)E;
+  g.config = cfg;
+  g.shared_weights = shared_weights ? 1 : 0;
+  g.store_pol = (int)store_pol;
+  if (out_ptrs.has_value()) {
+    TORCH_CHECK((int64_t)outs.size() == E && out_ptrs->is_cuda() && out_ptrs->scalar_type() == at::kLong &&
+                    out_ptrs->numel() == E,
+                "compact outputs: E tensors + int64 [E] addresses");
+    const int64_t cap = outs[0].size(0);
+    for (const auto& o : outs) {
+      check_bf16(o, "expert output");
+      TORCH_CHECK(o.dim() == 2 && o.is_contiguous() && o.size(1) == NO && o.size(0) == cap,
+                  "expert outputs: E contiguous [cap][N'] tensors");
+    }
+    g.ldc = (int)NO;
+    g.compact_rows = (int)cap;
+    g.c_ptrs = reinterpret_cast<const unsigned long long*>(out_ptrs->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(out.has_value(), "grouped GEMM needs `out` or compact outputs");
+    check_bf16(*out, "out");
+    TORCH_CHECK(out->dim() == 2 && out->stride(1) == 1, "out must be 2-D with contiguous rows");
+    TORCH_CHECK(out->size(0) == R && out->size(1) == NO, "out must be [R][N'] (N' = N/2 with SwiGLU)");
+    g.C = out->data_ptr();
+    g.ldc = (int)out->stride(0);
+  }
+  if (R == 0) return;
+  launch_gemm_w8_grouped(g, cur_stream());
+}
+
 // experts: list of E compact [rows][H] bf16 outputs; ptrs: int64 [E] device tensor holding
 // their addresses (built once by the caller and cached — hipGraph-safe)
 at::Tensor moe_gather_combine(const std::vector<at::Tensor>& experts, const at::Tensor& ptrs, const at::Tensor& idx,
@@ -966,6 +1051,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     gemm_w8_pick(M, N, K, &c, &s);
     return std::make_pair(c, s);
   });
+  m.def("gemm_grouped_w8", &gemm_grouped_w8, py::arg("x"), py::arg("weights"), py::arg("scales"), py::arg("w_ptrs"),
+        py::arg("s_ptrs"), py::arg("offsets"), py::arg("act") = 0, py::arg("out") = py::none(),
+        py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(), py::arg("config") = -1,
+        py::arg("rows_hint") = 0, py::arg("a_rows") = py::none(), py::arg("shared_weights") = false,
+        py::arg("store_pol") = 0);
+  m.def("gemm_w8_grouped_num_configs", &gemm_w8_grouped_num_configs);
+  m.def("gemm_w8_grouped_tile_rows", &gemm_w8_grouped_tile_rows);
+  m.def("gemm_w8_grouped_pick", &gemm_w8_grouped_pick);
   m.attr("REGSTAGE") = kRegStage;
   m.attr("PERSIST") = kGemmPersist;
   m.def("gemm_pick_config", &gemm_pick_config);

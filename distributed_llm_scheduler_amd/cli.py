@@ -19,7 +19,8 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
 --tp, --sp, --seed, --dtype (bf16: the kernels compute in bf16 with fp32 accumulation),
---weight-dtype {bf16,fp8} (how GEMM weights are STORED: fp8 = e4m3 + one fp32 scale per output channel).
+--weight-dtype {bf16,fp8,fp8-experts} (how GEMM weights are STORED: fp8 = e4m3 + one fp32 scale per
+output channel, dense models; fp8-experts = the same for the expert weights of an MoE model only).
 """
 from __future__ import annotations
 
@@ -50,9 +51,11 @@ def _common(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--dtype", default="bf16", choices=["bf16"],
                     help="compute dtype of activations and MFMA operands (bf16, fp32 accumulation); the storage of "
                          "the GEMM weights is selectable with --weight-dtype")
-    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp8-experts"],
                     help="GEMM weight storage: bf16, or fp8 (OCP e4m3 + one fp32 scale per output channel; dense "
-                         "models, no --tp / --sp): about half the parameter bytes under the same --hbm-cap-gb")
+                         "models, no --tp / --sp): about half the parameter bytes under the same --hbm-cap-gb; "
+                         "fp8-experts: the same storage for the expert weights of an MoE model (router, attention "
+                         "and LM head stay bf16; no --tp / --sp)")
     ap.add_argument("--no-fuse", action="store_true")
 
 

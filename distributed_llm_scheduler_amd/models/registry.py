@@ -29,23 +29,28 @@ def build_dag(cfg: ModelConfig, batch: int = 1, seq: int = 512, cost_model: str 
     raise KeyError(cfg.family)
 
 
-WEIGHT_DTYPES = ("bf16", "fp8")
+WEIGHT_DTYPES = ("bf16", "fp8", "fp8-experts")
 # (op kind, weight key) pairs that read a tensor as a GEMM weight operand
 _GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("attention", "w_o"),
                   ("swiglu_mlp", "w_gate_up"), ("swiglu_mlp", "w_down")}
+# the expert GEMM weights of an MoE layer (weight_dtype="fp8-experts"); the router weight
+# (moe.gate, read by a "linear" node) is not among them
+_EXPERT_OPERANDS = {("moe_expert", "w_gate_up"), ("moe_expert", "w_down")}
 
 
-def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup]) -> List[str]:
-    """Mark for fp8 storage (``TensorSpec.quant``) every tensor that EVERY reader reads as a
-    GEMM weight operand. Embedding tables, norm gains, biases and a weight an embedding also
-    gathers from (GPT-2's tied ``wte``) stay bf16. Returns the marked names."""
+def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OPERANDS) -> List[str]:
+    """Mark for fp8 storage (``TensorSpec.quant``) every tensor that EVERY reader reads as one
+    of ``operands`` — (op kind, weight key) pairs: by default the GEMM weight operands of a
+    dense model, ``_EXPERT_OPERANDS`` for the experts of an MoE model. Embedding tables, norm
+    gains, biases and a weight an embedding also gathers from (GPT-2's tied ``wte``) stay bf16.
+    Returns the marked names."""
     gemm, other = set(), set()
     for t in tasks:
         if t.op is None:
             continue
         for key, name in t.op.weights.items():
             if isinstance(name, str):
-                (gemm if (t.op.kind, key) in _GEMM_OPERANDS else other).add(name)
+                (gemm if (t.op.kind, key) in operands else other).add(name)
     marked = []
     for g in groups.values():
         for sp in g.tensors:
@@ -61,15 +66,25 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
     of a dense model are stored as e4m3 with one fp32 scale per output channel
-    (:func:`mark_fp8`); not with MoE models, ``tp`` or ``sp``."""
+    (:func:`mark_fp8`); not with MoE models, ``tp`` or ``sp``. ``weight_dtype="fp8-experts"``: the
+    same storage for the expert weights (``w_gate_up``, ``w_down``) of an MoE model only — router,
+    attention and LM head stay bf16; not with a model without experts, ``tp`` or ``sp``."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     cfg = get_config(model)
     if weight_dtype == "fp8":
         if cfg.n_experts:
-            raise ValueError("weight_dtype='fp8' does not cover MoE models (the grouped expert GEMM is bf16)")
+            raise ValueError("weight_dtype='fp8' does not cover MoE models: weight_dtype='fp8-experts' stores "
+                             "their expert weights as fp8 (attention, router and LM head stay bf16)")
         if tp > 1 or sp > 1:
             raise ValueError("weight_dtype='fp8' does not combine with tensor or sequence parallelism (tp, sp > 1)")
+    if weight_dtype == "fp8-experts":
+        if not cfg.n_experts:
+            raise ValueError(f"weight_dtype='fp8-experts' needs an MoE model; {model} has no experts "
+                             "(weight_dtype='fp8' covers dense models)")
+        if tp > 1 or sp > 1:
+            raise ValueError("weight_dtype='fp8-experts' does not combine with tensor or sequence parallelism "
+                             "(tp, sp > 1)")
     tasks: List[Task] = []
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
@@ -84,4 +99,6 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         tasks, groups = sequence_parallel(tasks, groups, cfg, sp)
     if weight_dtype == "fp8":
         mark_fp8(tasks, groups)
+    elif weight_dtype == "fp8-experts":
+        mark_fp8(tasks, groups, _EXPERT_OPERANDS)
     return tasks, groups, cfg

@@ -800,6 +800,59 @@ def gemm_grouped(x, weights, offsets, act=None, out=None, outs=None, w_ptrs=None
     return out if outs is None else outs
 
 
+def w8_grouped_configs() -> int:
+    """Number of tile configurations of the grouped fp8-weight GEMM (``gemm_grouped_w8(config=...)``)."""
+    return int(ext().gemm_w8_grouped_num_configs())
+
+
+def w8_grouped_tile_rows(config: int) -> int:
+    """Row-tile height of a grouped fp8-weight GEMM configuration (a group of more rows takes
+    several passes of its block)."""
+    return int(ext().gemm_w8_grouped_tile_rows(int(config)))
+
+
+def gemm_grouped_w8(x, qweights, scales, offsets, act=None, out=None, outs=None, w_ptrs=None, s_ptrs=None,
+                    out_ptrs=None, rows_hint=None, a_rows=None, shared_weights=False, config=None):
+    """:func:`gemm_grouped` with fp8 expert weights: group g multiplies its rows by
+    ``qweights[g]`` (``float8_e4m3fn`` [N][K], K % 16 == 0) and ``scales[g]`` (fp32 [N], any
+    positive values; applied once, after the fp32 accumulation). ``act``: ``None`` or
+    ``"swiglu"`` (rows of q AND scale gate/up-interleaved in blocks of ``SWIGLU_BLOCK``, N/2
+    outputs). Rows, ``a_rows``, ``out`` / compact ``outs`` and ``shared_weights`` as in
+    :func:`gemm_grouped`; ``s_ptrs`` is the cached int64 device tensor of the scales' addresses,
+    next to ``w_ptrs`` / ``out_ptrs`` (all built here when omitted — pass cached ones inside a
+    hipGraph). GPU: ONE launch of gemm_w8_grouped.hip (the fp8 bytes go global -> registers,
+    are converted to bf16 there and multiplied on the bf16 MFMA; no split-K, no atomics:
+    bitwise reproducible). ``config``: ``None`` picks by ``(rows_hint, N, K)``; ``c`` forces tile
+    configuration c (< :func:`w8_grouped_configs`). CPU tensors run :func:`gemm_grouped`'s
+    reference loop on the dequantised weights."""
+    a = ACT[act] if not isinstance(act, int) else act
+    for q in qweights:
+        if q.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"gemm_grouped_w8: the weights must be float8_e4m3fn, got {q.dtype}")
+    if a not in (0, SWIGLU):
+        raise ValueError("gemm_grouped_w8: act is None or 'swiglu'")
+    E = len(qweights)
+    N, K = qweights[0].shape
+    R = x.shape[0] if a_rows is None else a_rows.numel()
+    if _gpu(x):
+        mk = lambda ts: torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=x.device)  # noqa: E731
+        if w_ptrs is None:
+            w_ptrs = mk(qweights)
+        if s_ptrs is None:
+            s_ptrs = mk(scales)
+        if outs is not None and out_ptrs is None:
+            out_ptrs = mk(outs)
+        ext().gemm_grouped_w8(x, list(qweights), list(scales), w_ptrs, s_ptrs, offsets, a, out,
+                              list(outs) if outs is not None else [], out_ptrs,
+                              -1 if config is None else int(config), int(rows_hint or max(1, R // E)), a_rows,
+                              bool(shared_weights), _stream_pol(N, K) & 6)
+        return out if outs is None else outs
+    if K % 16:
+        raise ValueError(f"gemm_grouped_w8: K must be a multiple of 16, got {K}")
+    deq = [dequantize_fp8(q, s, torch.float32) for q, s in zip(qweights, scales)]
+    return gemm_grouped(x, deq, offsets, act=act, out=out, outs=outs, a_rows=a_rows)
+
+
 def grouped_gemm(X, offsets, W, act=None):
     """Per-expert ``act(X_e @ W_e^T)`` over expert-sorted rows; W is [E][N][K]."""
     a = ACT[act] if not isinstance(act, int) else act

@@ -541,11 +541,19 @@ class DAGExecutor:
         offsets, a_rows = bufs
         ops.moe_xbatch_index([rt[4] for rt in routes], [reqs.index((t.op.inputs[0], t.op.inputs[1])) for t in tasks],
                              [t.op.attrs["expert"] for t in tasks], [q * R for q in range(len(reqs))], offsets, a_rows)
-        w13 = [self._prep(t.op.weights["w_gate_up"], None, None, interleave=True)[0] for t in tasks]
-        w2 = [self._w(t.op.weights["w_down"]) for t in tasks]
         outs = [self._flat(self._views[t.id]) for t in tasks]
         hbuf = self._scratch("moe_h", (len(reqs) * R, F))
         hint = max(1, R // E)
+        if self._moe_w8(tasks):  # fp8 expert weights: the grouped W8A16 kernel, same groups and rows
+            q13, s13, q2, s2 = self._moe_w8_weights(tasks)
+            pt = self._moe_w8_ptrs(("x", i), q13, s13, q2, s2, outs) if self.gpu else (None,) * 5
+            ops.gemm_grouped_w8(xp, q13, s13, offsets, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                rows_hint=hint, a_rows=a_rows, shared_weights=True)
+            ops.gemm_grouped_w8(hbuf, q2, s2, offsets, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                rows_hint=hint, shared_weights=True)
+            return
+        w13 = [self._prep(t.op.weights["w_gate_up"], None, None, interleave=True)[0] for t in tasks]
+        w2 = [self._w(t.op.weights["w_down"]) for t in tasks]
         if not self.gpu:
             ops.gemm_grouped(xp, w13, offsets, act="swiglu", out=hbuf, rows_hint=hint, a_rows=a_rows)
             ops.gemm_grouped(hbuf, w2, offsets, outs=outs, rows_hint=hint)
@@ -630,9 +638,18 @@ class DAGExecutor:
         else:
             x, rows = self._moe_permuted(tasks[0].op.inputs[0], tasks[0].op.inputs[1], E, K), None
         R, F = src.numel(), a["ffn"]
+        outs = [self._flat(self._views[t.id]) for t in tasks]
+        if self._moe_w8(tasks):  # fp8 expert weights: the grouped W8A16 kernel, same groups and rows
+            q13, s13, q2, s2 = self._moe_w8_weights(tasks)
+            pt = self._moe_w8_ptrs(i, q13, s13, q2, s2, outs)
+            hbuf = self._scratch("moe_h", (R, F))
+            ops.gemm_grouped_w8(x, q13, s13, off, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                rows_hint=max(1, R // E), a_rows=rows)
+            ops.gemm_grouped_w8(hbuf, q2, s2, off, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                rows_hint=max(1, R // E))
+            return
         w13 = [self._prep(t.op.weights["w_gate_up"], None, None, interleave=True)[0] for t in tasks]
         w2 = [self._w(t.op.weights["w_down"]) for t in tasks]
-        outs = [self._flat(self._views[t.id]) for t in tasks]
         ptrs = tuple(w.data_ptr() for w in w13 + w2 + outs)
         cached = self._moe_bufs.get(i)
         if cached is None or cached[0] != ptrs:
@@ -642,6 +659,40 @@ class DAGExecutor:
         hbuf = self._scratch("moe_h", (R, F))
         ops.gemm_grouped(x, w13, off, act="swiglu", out=hbuf, w_ptrs=cached[1], rows_hint=max(1, R // E), a_rows=rows)
         ops.gemm_grouped(hbuf, w2, off, outs=outs, w_ptrs=cached[2], out_ptrs=cached[3], rows_hint=max(1, R // E))
+
+    def _moe_w8(self, tasks) -> bool:
+        """Are these expert nodes' weights stored as fp8 (weight_dtype="fp8-experts")?"""
+        return bool(self._q_names) and tasks[0].op.weights["w_gate_up"] in self._q_names
+
+    def _moe_w8_weights(self, tasks):
+        """(q13, s13, q2, s2) of the expert nodes: e4m3 weights and their fp32 channel scales, the
+        gate/up rows of q AND scale interleaved for the SwiGLU epilogue (once per fill, persisted
+        into the host image: _prep_w8)."""
+        q13, s13, q2, s2 = [], [], [], []
+        for t in tasks:
+            n13, n2 = t.op.weights["w_gate_up"], t.op.weights["w_down"]
+            q, sc = self._w(n13), self._w(n13 + SCALE_SUFFIX)
+            self._prep_w8(n13, q, sc, None)
+            q13.append(q)
+            s13.append(sc)
+            q2.append(self._w(n2))
+            s2.append(self._w(n2 + SCALE_SUFFIX))
+        return q13, s13, q2, s2
+
+    def _moe_w8_ptrs(self, key, q13, s13, q2, s2, outs):
+        """Cached device arrays of the groups' addresses (gate/up weights, their scales, down
+        weights, their scales, outputs). The cache key holds the addresses themselves: a refill
+        into another region builds NEW arrays (in an eager step) and the earlier ones stay as they
+        are, so a captured step that recorded them keeps replaying valid memory."""
+        ptrs = tuple(t.data_ptr() for t in q13 + s13 + q2 + s2 + outs)
+        cached = self._moe_bufs.get(("w8", key, ptrs))
+        if cached is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fp8 expert pointer arrays must be built before hipGraph capture")
+            mk = lambda ts: torch.tensor([x.data_ptr() for x in ts], dtype=torch.int64, device=self.device)  # noqa: E731
+            cached = (mk(q13), mk(s13), mk(q2), mk(s2), mk(outs))
+            self._moe_bufs[("w8", key, ptrs)] = cached
+        return cached
 
     def _plan_prefetch(self) -> None:
         """For every ``load`` at instruction i: the earliest point it may start — right after
@@ -1332,6 +1383,14 @@ class DAGExecutor:
         R, F = xp.shape[0], a["ffn"]
         hint = max(1, R // E)
         hbuf = self._scratch("moe_h", (R, F))
+        if self._moe_w8([t]):  # fp8 expert weights: a one-group launch pair of the grouped W8A16 kernel
+            q13, s13, q2, s2 = self._moe_w8_weights([t])
+            o2 = [self._flat(out)]
+            pt = self._moe_w8_ptrs(("e", t.id), q13, s13, q2, s2, o2) if self.gpu else (None,) * 5
+            ops.gemm_grouped_w8(xp, q13, s13, rows, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1], rows_hint=hint)
+            ops.gemm_grouped_w8(hbuf, q2, s2, rows, outs=o2, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                rows_hint=hint)
+            return
         W13, _, _ = self._prep(W["w_gate_up"], None, None, interleave=True)
         ops.linear(xp, W13, act="swiglu", out=hbuf, rows=rows, rows_hint=hint)
         ops.linear(hbuf, self._w(W["w_down"]), out=out, rows=rows, rows_hint=hint, compact=True)

@@ -103,7 +103,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     ``weight_dtype="fp8"``: the GEMM weights of a dense model are stored (and budgeted, filled
     and multiplied) as e4m3 bytes with one fp32 scale per output channel (registry.mark_fp8):
     about half the parameter bytes under the same cap. Raises ``ValueError`` with an MoE model,
-    ``tp > 1`` or ``sp > 1``.
+    ``tp > 1`` or ``sp > 1``. ``weight_dtype="fp8-experts"``: the same storage for the expert
+    weights of an MoE model only (router, attention and LM head stay bf16); raises ``ValueError``
+    with a model without experts, ``tp > 1`` or ``sp > 1``.
 
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
