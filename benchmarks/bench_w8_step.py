@@ -6,7 +6,11 @@ step and kernel launches of the captured step. One JSON line per run.
     python benchmarks/bench_w8_step.py --model llama3-8b --cap 10.3 [--scheduler EFT] [--rounds 2]
     python benchmarks/bench_w8_step.py --model mixtral-8x7b --weight-dtype fp8-experts [--cap 65.4]
 
-``--weight-dtype D`` runs bf16 next to D (``--modes`` lists the modes explicitly).
+    python benchmarks/bench_w8_step.py --model llama3-8b --modes bf16,fp8,fp8+a8
+
+``--weight-dtype D`` runs bf16 next to D (``--modes`` lists the modes explicitly). Mode ``fp8+a8``
+is fp8 weights with fp8 activations (``act_dtype="fp8"``: the fp8 x fp8 GEMM); ``--act-dtype fp8``
+adds it to the default modes.
 """
 from __future__ import annotations
 
@@ -23,9 +27,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
 
 
-def run(model, cap, sched, wd, steps, warmup):
+def run(model, cap, sched, mode, steps, warmup):
     dev = torch.device("cuda:0")
-    p = runtime.plan(model, world=1, scheduler=sched, cap_gb=cap, cost_model="bytes", weight_dtype=wd)
+    wd, ad = (mode[:-3], "fp8") if mode.endswith("+a8") else (mode, "bf16")
+    p = runtime.plan(model, world=1, scheduler=sched, cap_gb=cap, cost_model="bytes", weight_dtype=wd, act_dtype=ad)
     store = runtime.make_store(p, device_init=runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store)
     for _ in range(warmup):
@@ -39,7 +44,7 @@ def run(model, cap, sched, wd, steps, warmup):
         st = ex.step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
-    out = {"model": model, "weight_dtype": wd, "scheduler": p.scheduler_name, "cap_gb": cap,
+    out = {"model": model, "weight_dtype": wd, "act_dtype": ad, "scheduler": p.scheduler_name, "cap_gb": cap,
            "param_gb": round(sum(p.param_bytes.values()) / 1e9, 3), "tasks_completed": p.completed,
            "tasks_total": p.total, "ms_per_step": round(ms, 3),
            "refill_gb_per_step_planned": round(p.stats["refill_gb_per_step_per_rank"][0], 3),
@@ -60,13 +65,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--weight-dtype", default="fp8", choices=["fp8", "fp8-experts"],
                     help="the fp8 mode measured next to bf16 (fp8-experts: the MoE models)")
-    ap.add_argument("--modes", default=None, help="comma-separated weight dtypes (default: bf16,<--weight-dtype>)")
+    ap.add_argument("--act-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: also run <--weight-dtype>+a8 (fp8 activations; with --weight-dtype fp8)")
+    ap.add_argument("--modes", default=None,
+                    help="comma-separated modes: a weight dtype, or fp8+a8 (default: bf16,<--weight-dtype>)")
     a = ap.parse_args()
     if a.modes is None:
-        a.modes = "bf16," + a.weight_dtype
+        a.modes = "bf16," + a.weight_dtype + ("," + a.weight_dtype + "+a8" if a.act_dtype == "fp8" else "")
     for _ in range(a.rounds):
-        for wd in a.modes.split(","):
-            print(json.dumps(run(a.model, a.cap, a.scheduler, wd, a.steps, a.warmup)), flush=True)
+        for mode in a.modes.split(","):
+            print(json.dumps(run(a.model, a.cap, a.scheduler, mode, a.steps, a.warmup)), flush=True)
 
 
 if __name__ == "__main__":

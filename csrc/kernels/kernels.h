@@ -165,6 +165,47 @@ int gemm_w8_grouped_tile_rows(int cfg);  // row-tile height of a config
 int gemm_w8_grouped_pick(int rows_hint, int N, int K, int n_groups);
 void launch_gemm_w8_grouped(const GemmW8GroupedArgs& a, hipStream_t s);
 
+// W8A8 GEMM (gemm_w8a8.hip): C = act(alpha * xscale[m] * scale[n] * sum_k Aq[m][k] * Wq[n][k] +
+// bias[n]) + R with BOTH operands OCP e4m3 bytes (K contiguous), one fp32 scale per activation
+// row and one per output channel, on the block-scaled fp8 MFMA (16x16x128, neutral block
+// scales); the two scales are applied in the epilogue. K % 16 == 0, any M, N (even for SwiGLU).
+struct GemmW8A8Args {
+  const void* Aq;  // e4m3 [M][lda]
+  int lda;
+  const float* xscale;  // fp32 [M], positive
+  const void* Wq;       // e4m3 [N][ldw]
+  int ldw;
+  const float* scale;  // fp32 [N], positive
+  void* C;             // bf16 [M][ldc] (SwiGLU: N/2 columns)
+  int ldc;
+  const void* bias;  // bf16 [N] or nullptr
+  const void* R;     // bf16 [M][ldr] or nullptr
+  int ldr;
+  int M, N, K;
+  int act;  // DlsAct
+  float alpha;
+  int config;        // 0..gemm_w8a8_num_configs()-1
+  int splitk;        // >= 1; > 1: fp32 partial slabs in `workspace`, summed in a fixed order
+  float* workspace;  // gemm_w8a8_workspace_bytes() when splitk > 1
+  int store_pol;     // as GemmW8Args::store_pol
+};
+int gemm_w8a8_num_configs();
+void gemm_w8a8_pick(int M, int N, int K, int* cfg, int* splitk);
+int gemm_w8a8_max_splitk(int cfg, int K);
+size_t gemm_w8a8_workspace_bytes(int M, int N, int splitk);
+void launch_gemm_w8a8(const GemmW8A8Args& a, hipStream_t s);
+
+// Per-row e4m3 quantisation (quant_rows.hip): q[m][k] = rne(x[m][k] / scale[m]) with scale[m] the
+// smallest power of two with amax_m / scale[m] <= 448 (all-zero row: 1). x bf16 [M][ldx],
+// q e4m3 [M][ldq], K % 8 == 0.
+void launch_quant_rows_fp8(const void* x, int ldx, void* q, int ldq, float* scale, int M, int K, hipStream_t s);
+// launch_layernorm / launch_rmsnorm emitting the quantised rows of their (bf16-rounded) output:
+// q e4m3 [M][H] contiguous, scale fp32 [M]
+void launch_layernorm_q8(const void* x, const void* r, void* sum_out, const void* w, const void* b, void* q,
+                         float* scale, int M, int H, float eps, hipStream_t s);
+void launch_rmsnorm_q8(const void* x, const void* r, void* sum_out, const void* w, void* q, float* scale, int M,
+                       int H, float eps, hipStream_t s);
+
 struct AttnArgs {
   const void* q; int ldq;   // bf16, row = token (b*S + s), head h at column h*D
   const void* k; int ldk;   // kv head g at column g*D

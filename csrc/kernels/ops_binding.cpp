@@ -303,6 +303,160 @@ at::Tensor gemm_w8(const at::Tensor& a_in, const at::Tensor& wq, const at::Tenso
   return c;
 }
 
+// W8A8 GEMM (gemm_w8a8.hip): xq e4m3 [M][K] with fp32 row scales, wq e4m3 [N][K] with fp32 channel
+// scales. config / splitk / workspace as gemm_w8.
+at::Tensor gemm_w8a8(const at::Tensor& xq_in, const at::Tensor& xscale, const at::Tensor& wq,
+                     const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& residual, int64_t act, double alpha,
+                     const c10::optional<at::Tensor>& out, int64_t config, int64_t splitk, int64_t store_pol,
+                     const c10::optional<at::Tensor>& workspace) {
+  TORCH_CHECK(xq_in.is_cuda() && xq_in.scalar_type() == at::kFloat8_e4m3fn, "xq must be a float8_e4m3fn GPU tensor");
+  at::Tensor a = as2d(xq_in);
+  TORCH_CHECK(wq.is_cuda() && wq.device() == a.device() && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "W must be a float8_e4m3fn tensor on xq's GPU");
+  TORCH_CHECK(wq.dim() == 2, "W must be 2-D");
+  const int64_t M = a.size(0), K = a.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K, "W must be [N][K] with K = ", K, ", got ", wq.sizes());
+  TORCH_CHECK(K % 16 == 0, "the fp8 GEMM needs K % 16 == 0, got K = ", K);
+  TORCH_CHECK(a.stride(1) == 1 && a.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "xq must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(wq.stride(1) == 1 && wq.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+              "W must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(xscale.is_cuda() && xscale.device() == a.device() && xscale.scalar_type() == at::kFloat &&
+                  xscale.is_contiguous() && xscale.numel() == M,
+              "xscale must be a contiguous fp32 [M] tensor on xq's GPU");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == a.device() && scale.scalar_type() == at::kFloat &&
+                  scale.is_contiguous() && scale.numel() == N,
+              "scale must be a contiguous fp32 [N] tensor on xq's GPU");
+  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
+  const bool swiglu = act == kActSwiglu;
+  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
+  const int64_t NO = swiglu ? N / 2 : N;
+  const auto bf = a.options().dtype(at::kBFloat16);
+  at::Tensor c;
+  if (out.has_value()) {
+    c = as2d(*out);
+    check_bf16(c, "out");
+    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
+                "out must be [M][N_out] with contiguous rows");
+  } else {
+    c = at::empty({M, NO}, bf);
+  }
+  const void* bptr = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
+    bptr = bias->data_ptr();
+  }
+  const void* rptr = nullptr;
+  int ldr = 0;
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
+    rptr = r.data_ptr();
+    ldr = (int)r.stride(0);
+  }
+  if (M == 0 || N == 0) return c;
+  int cfg = (int)config, sk = (int)splitk;
+  if (cfg < 0 || sk <= 0) {
+    int acfg, ask;
+    gemm_w8a8_pick((int)M, (int)N, (int)K, &acfg, &ask);
+    if (cfg < 0) {
+      cfg = acfg;
+      if (sk <= 0) sk = ask;
+    } else if (sk <= 0) {
+      sk = 1;
+    }
+  }
+  TORCH_CHECK(cfg < gemm_w8a8_num_configs(), "unknown fp8 GEMM config ", cfg);
+  sk = std::min(sk, gemm_w8a8_max_splitk(cfg, (int)K));
+  at::Tensor ws;
+  if (sk > 1) {
+    const int64_t need = (int64_t)gemm_w8a8_workspace_bytes((int)M, (int)N, sk) / 4;
+    if (workspace.has_value()) {
+      ws = *workspace;
+      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
+                      ws.is_contiguous() && ws.numel() >= need,
+                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
+    } else {
+      ws = at::empty({need}, a.options().dtype(at::kFloat));
+    }
+  }
+  GemmW8A8Args g{a.data_ptr(), (int)a.stride(0), xscale.data_ptr<float>(), wq.data_ptr(), (int)wq.stride(0),
+                 scale.data_ptr<float>(), c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K,
+                 (int)act, (float)alpha, cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+  launch_gemm_w8a8(g, cur_stream());
+  return c;
+}
+
+// (q, scale) outputs of the row quantisers: e4m3 [M][K] contiguous rows and fp32 [M], the
+// caller's (checked) or fresh ones
+std::pair<at::Tensor, at::Tensor> q8_outputs(const at::Tensor& like, int64_t M, int64_t K,
+                                             const c10::optional<at::Tensor>& out_q,
+                                             const c10::optional<at::Tensor>& out_scale) {
+  at::Tensor q = out_q.has_value() ? as2d(*out_q) : at::empty({M, K}, like.options().dtype(at::kFloat8_e4m3fn));
+  TORCH_CHECK(q.is_cuda() && q.device() == like.device() && q.element_size() == 1 && q.is_contiguous() &&
+                  q.size(0) == M && q.size(1) == K && reinterpret_cast<uintptr_t>(q.data_ptr()) % 8 == 0,
+              "out_q must be a contiguous 1-byte [M][K] GPU tensor");
+  at::Tensor s = out_scale.has_value() ? *out_scale : at::empty({M}, like.options().dtype(at::kFloat));
+  TORCH_CHECK(s.is_cuda() && s.device() == like.device() && s.scalar_type() == at::kFloat && s.is_contiguous() &&
+                  s.numel() == M,
+              "out_scale must be a contiguous fp32 [M] GPU tensor");
+  return {q, s};
+}
+
+// per-row e4m3 quantisation of bf16 rows (quant_rows.hip): one launch, no allocation when both
+// outputs are given
+std::vector<at::Tensor> quantize_rows_fp8(const at::Tensor& x_in, const c10::optional<at::Tensor>& out_q,
+                                          const c10::optional<at::Tensor>& out_scale) {
+  check_bf16(x_in, "x");
+  at::Tensor x = as2d(x_in);
+  check_rows(x, "x");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K % 8 == 0, "row quantiser needs K % 8 == 0, got K = ", K);
+  auto [q, s] = q8_outputs(x, M, K, out_q, out_scale);
+  if (M > 0 && K > 0)
+    launch_quant_rows_fp8(x.data_ptr(), (int)x.stride(0), q.data_ptr(), (int)q.stride(0), s.data_ptr<float>(), (int)M,
+                          (int)K, cur_stream());
+  return {q, s};
+}
+
+// norm() emitting the quantised rows of its output: returns (q, scale, sum)
+std::vector<at::Tensor> norm_q8(const at::Tensor& x_in, const at::Tensor& w, const c10::optional<at::Tensor>& b,
+                                double eps, const c10::optional<at::Tensor>& residual, bool rms,
+                                const c10::optional<at::Tensor>& sum_out, const c10::optional<at::Tensor>& out_q,
+                                const c10::optional<at::Tensor>& out_scale) {
+  check_bf16(x_in, "x");
+  at::Tensor x = as2d(x_in).contiguous();
+  const int64_t M = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 8 == 0 && H <= 8192, "hidden size must be a multiple of 8 and <= 8192");
+  check_bf16(w, "weight");
+  TORCH_CHECK(w.is_contiguous() && w.numel() == H, "weight must be contiguous [H]");
+  if (b.has_value()) {
+    check_bf16(*b, "bias");
+    TORCH_CHECK(b->is_contiguous() && b->numel() == H, "bias must be contiguous [H]");
+  }
+  auto [q, sc] = q8_outputs(x, M, H, out_q, out_scale);
+  at::Tensor r, s;
+  if (residual.has_value()) {
+    r = as2d(*residual).contiguous();
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.sizes() == x.sizes(), "residual must match x");
+    s = sum_out.has_value() ? as2d(*sum_out) : at::empty({M, H}, x.options());
+    TORCH_CHECK(s.is_contiguous(), "sum_out must be contiguous");
+  }
+  if (M == 0) return {q, sc, s};
+  if (rms)
+    launch_rmsnorm_q8(x.data_ptr(), r.defined() ? r.data_ptr() : nullptr, s.defined() ? s.data_ptr() : nullptr,
+                      w.data_ptr(), q.data_ptr(), sc.data_ptr<float>(), (int)M, (int)H, (float)eps, cur_stream());
+  else
+    launch_layernorm_q8(x.data_ptr(), r.defined() ? r.data_ptr() : nullptr, s.defined() ? s.data_ptr() : nullptr,
+                        w.data_ptr(), b.has_value() ? b->data_ptr() : nullptr, q.data_ptr(), sc.data_ptr<float>(),
+                        (int)M, (int)H, (float)eps, cur_stream());
+  return {q, sc, s};
+}
+
 at::Tensor attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t B, int64_t S,
                      int64_t n_head, int64_t n_kv_head, int64_t head_dim, bool causal, double scale,
                      const c10::optional<at::Tensor>& out, int64_t variant, int64_t Sq, int64_t q_off,
@@ -1076,6 +1230,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("norm", &norm, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5,
         py::arg("residual") = py::none(), py::arg("rms") = false, py::arg("out") = py::none(),
         py::arg("sum_out") = py::none());
+  m.def("gemm_w8a8", &gemm_w8a8, py::arg("xq"), py::arg("xscale"), py::arg("wq"), py::arg("scale"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0,
+        py::arg("out") = py::none(), py::arg("config") = -1, py::arg("splitk") = 0, py::arg("store_pol") = 0,
+        py::arg("workspace") = py::none());
+  m.def("gemm_w8a8_num_configs", &gemm_w8a8_num_configs);
+  m.def("gemm_w8a8_pick", [](int M, int N, int K) {
+    int c, s;
+    gemm_w8a8_pick(M, N, K, &c, &s);
+    return std::make_pair(c, s);
+  });
+  m.def("quantize_rows_fp8", &quantize_rows_fp8, py::arg("x"), py::arg("out_q") = py::none(),
+        py::arg("out_scale") = py::none());
+  m.def("norm_q8", &norm_q8, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5,
+        py::arg("residual") = py::none(), py::arg("rms") = false, py::arg("sum_out") = py::none(),
+        py::arg("out_q") = py::none(), py::arg("out_scale") = py::none());
   m.def("gelu", &gelu, py::arg("x"), py::arg("out") = py::none());
   m.def("add", &add, py::arg("a"), py::arg("b"), py::arg("out") = py::none());
   m.def("swiglu", &swiglu, py::arg("gate_up"), py::arg("out") = py::none());

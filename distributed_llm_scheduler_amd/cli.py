@@ -20,7 +20,8 @@ Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
 --tp, --sp, --seed, --dtype (bf16: the kernels compute in bf16 with fp32 accumulation),
 --weight-dtype {bf16,fp8,fp8-experts} (how GEMM weights are STORED: fp8 = e4m3 + one fp32 scale per
-output channel, dense models; fp8-experts = the same for the expert weights of an MoE model only).
+output channel, dense models; fp8-experts = the same for the expert weights of an MoE model only),
+--act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8: GEMM inputs quantised per row, fp8 x fp8 MFMA).
 """
 from __future__ import annotations
 
@@ -56,6 +57,9 @@ def _common(ap: argparse.ArgumentParser) -> None:
                          "models, no --tp / --sp): about half the parameter bytes under the same --hbm-cap-gb; "
                          "fp8-experts: the same storage for the expert weights of an MoE model (router, attention "
                          "and LM head stay bf16; no --tp / --sp)")
+    ap.add_argument("--act-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="GEMM input dtype over fp8 weights: bf16 (the W8A16 kernel), or fp8 (needs --weight-dtype "
+                         "fp8: rows quantised to e4m3 with one power-of-two scale each, multiplied on the fp8 MFMA)")
     ap.add_argument("--no-fuse", action="store_true")
 
 
@@ -64,7 +68,8 @@ def _plan(a, world: int, resume: Optional[str] = None):
 
     return runtime.plan(a.model, world=world, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, replicas=a.replicas,
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
-                        placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype)
+                        placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
+                        act_dtype=a.act_dtype)
 
 
 def _param_gb(p) -> float:
@@ -77,7 +82,7 @@ def cmd_plan(a) -> int:
     t0 = time.time()
     p = _plan(a, a.devices)
     out = {"model": a.model, "scheduler": p.scheduler_name, "world": p.world, "plan_ms": round((time.time() - t0) * 1e3, 2),
-           "weight_dtype": a.weight_dtype, "param_gb": _param_gb(p)}
+           "weight_dtype": a.weight_dtype, "act_dtype": a.act_dtype, "param_gb": _param_gb(p)}
     out.update(p.stats)
     print(json.dumps(out))
     if a.save:
@@ -216,7 +221,7 @@ def cmd_run(a) -> int:
                           "tasks_completed": p.stats["tasks_completed"], "tasks_total": p.stats["tasks_total"],
                           "ms_per_step": round(float(t[0].item()), 4), "device": str(dev),
                           "p2p": getattr(ex.comm, "kind", None), "valid": not invalid,
-                          "weight_dtype": a.weight_dtype, "param_gb": _param_gb(p)}))
+                          "weight_dtype": a.weight_dtype, "act_dtype": a.act_dtype, "param_gb": _param_gb(p)}))
         if events is not None:
             from .utils.tracing import chrome_trace, kernel_timeline
 
@@ -283,7 +288,7 @@ def cmd_elastic(a) -> int:
     out = run_elastic(world=a.devices, steps=a.steps, fail_rank=a.fail_rank, fail_step=a.fail_step,
                       device=a.device, model=a.model, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb,
                       replicas=a.replicas, batch=a.batch, seq=a.seq, cost_model=a.cost_model, placement=a.placement,
-                      tp=a.tp, sp=a.sp, weight_dtype=a.weight_dtype)
+                      tp=a.tp, sp=a.sp, weight_dtype=a.weight_dtype, act_dtype=a.act_dtype)
     print(json.dumps(out))
     return 0
 

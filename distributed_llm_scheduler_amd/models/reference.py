@@ -13,11 +13,27 @@ import torch
 import torch.nn.functional as F
 
 from .config import ModelConfig
-from .params import ParamStore
+from .params import ParamStore, dequantize_fp8, quantize_fp8
 
 
 def _w(store: ParamStore, name: str) -> torch.Tensor:
     return store.tensor(name).float()
+
+
+def _mm(store: ParamStore, x: torch.Tensor, name: str, a8: bool = False) -> torch.Tensor:
+    """``x @ W^T``; with fp8 activations (``a8``) and a weight the store holds quantised, the
+    input rows go through the per-row e4m3 quantise-dequantise first (quantize_fp8 of the rows:
+    one power-of-two scale per row)."""
+    if a8 and store.is_quantized(name):
+        q, s = quantize_fp8(x.reshape(-1, x.shape[-1]))
+        x = dequantize_fp8(q, s, torch.float32).reshape(x.shape)
+    return x @ _w(store, name).t()
+
+
+def _a8(act_dtype: str) -> bool:
+    if act_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"act_dtype must be 'bf16' or 'fp8', got {act_dtype!r}")
+    return act_dtype == "fp8"
 
 
 def _attn(q, k, v, nh, nkv, D, causal=True):
@@ -35,25 +51,27 @@ def _attn(q, k, v, nh, nkv, D, causal=True):
 
 
 @torch.no_grad()
-def gpt2_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, hidden: list = None) -> torch.Tensor:
+def gpt2_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, hidden: list = None,
+                 act_dtype: str = "bf16") -> torch.Tensor:
     """tokens [B, S] -> logits [B, S, V] (fp32). ``hidden`` (if a list) receives the residual
-    stream after every block."""
+    stream after every block. ``act_dtype``: see :func:`forward`."""
+    a8 = _a8(act_dtype)
     B, S = tokens.shape
     H, nh = cfg.n_embd, cfg.n_head
     x = _w(store, "wte")[tokens.long()] + _w(store, "wpe")[:S][None]
     for i in range(cfg.n_layer):
         p = f"h.{i}."
         h = F.layer_norm(x, (H,), _w(store, p + "ln_1.weight"), _w(store, p + "ln_1.bias"), cfg.norm_eps)
-        qkv = h @ _w(store, p + "attn.c_attn.weight").t() + _w(store, p + "attn.c_attn.bias")
+        qkv = _mm(store, h, p + "attn.c_attn.weight", a8) + _w(store, p + "attn.c_attn.bias")
         a = _attn(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], nh, nh, cfg.head_dim)
-        x = x + a @ _w(store, p + "attn.c_proj.weight").t() + _w(store, p + "attn.c_proj.bias")
+        x = x + _mm(store, a, p + "attn.c_proj.weight", a8) + _w(store, p + "attn.c_proj.bias")
         h = F.layer_norm(x, (H,), _w(store, p + "ln_2.weight"), _w(store, p + "ln_2.bias"), cfg.norm_eps)
-        h = F.gelu(h @ _w(store, p + "mlp.c_fc.weight").t() + _w(store, p + "mlp.c_fc.bias"), approximate="tanh")
-        x = x + h @ _w(store, p + "mlp.c_proj.weight").t() + _w(store, p + "mlp.c_proj.bias")
+        h = F.gelu(_mm(store, h, p + "mlp.c_fc.weight", a8) + _w(store, p + "mlp.c_fc.bias"), approximate="tanh")
+        x = x + _mm(store, h, p + "mlp.c_proj.weight", a8) + _w(store, p + "mlp.c_proj.bias")
         if hidden is not None:
             hidden.append(x.clone())
     x = F.layer_norm(x, (H,), _w(store, "ln_f.weight"), _w(store, "ln_f.bias"), cfg.norm_eps)
-    return x @ _w(store, "wte").t()
+    return _mm(store, x, "wte", a8)
 
 
 def _rope(x, S, D, theta):
@@ -72,23 +90,26 @@ def _rms(x, w, eps):
 
 
 @torch.no_grad()
-def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None) -> torch.Tensor:
+def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None,
+                  act_dtype: str = "bf16") -> torch.Tensor:
     """Llama-3 / Mixtral forward (fp32): tokens [B, S] -> logits [B, S, V]. ``router_margins``
     (if a list) receives, per MoE layer, the [B, S] gap between the k-th and (k+1)-th router
-    logit: tokens with a tiny gap may legitimately route differently under bf16 logits."""
+    logit: tokens with a tiny gap may legitimately route differently under bf16 logits.
+    ``act_dtype``: see :func:`forward`."""
+    a8 = _a8(act_dtype)
     B, S = tokens.shape
     nh, nkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
     x = _w(store, "tok_embeddings")[tokens.long()]
     for i in range(cfg.n_layer):
         p = f"layers.{i}."
         h = _rms(x, _w(store, p + "attention_norm.weight"), cfg.norm_eps)
-        qkv = h @ _w(store, p + "attention.wqkv").t()
+        qkv = _mm(store, h, p + "attention.wqkv", a8)
         q, k, v = qkv[..., :nh * D], qkv[..., nh * D:(nh + nkv) * D], qkv[..., (nh + nkv) * D:]
         q, k = _rope(q, S, D, cfg.rope_theta), _rope(k, S, D, cfg.rope_theta)
-        x = x + _attn(q, k, v, nh, nkv, D) @ _w(store, p + "attention.wo").t()
+        x = x + _mm(store, _attn(q, k, v, nh, nkv, D), p + "attention.wo", a8)
         h = _rms(x, _w(store, p + "ffn_norm.weight"), cfg.norm_eps)
         if cfg.n_experts:
-            logits = h @ _w(store, p + "moe.gate").t()
+            logits = _mm(store, h, p + "moe.gate", a8)
             val, idx = torch.topk(logits, cfg.top_k, -1)
             if router_margins is not None:
                 srt = torch.sort(logits, -1, descending=True).values
@@ -96,20 +117,25 @@ def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, rou
             gate = torch.softmax(val, -1)
             out = torch.zeros_like(h)
             for e in range(cfg.n_experts):
-                gu = h @ _w(store, p + f"moe.experts.{e}.w13").t()
+                gu = _mm(store, h, p + f"moe.experts.{e}.w13", a8)
                 y = F.silu(gu[..., :cfg.ffn]) * gu[..., cfg.ffn:]
-                y = y @ _w(store, p + f"moe.experts.{e}.w2").t()
+                y = _mm(store, y, p + f"moe.experts.{e}.w2", a8)
                 wgt = (gate * (idx == e)).sum(-1, keepdim=True)
                 out = out + wgt * y
             x = x + out
         else:
-            gu = h @ _w(store, p + "feed_forward.w13").t()
-            x = x + (F.silu(gu[..., :cfg.ffn]) * gu[..., cfg.ffn:]) @ _w(store, p + "feed_forward.w2").t()
+            gu = _mm(store, h, p + "feed_forward.w13", a8)
+            x = x + _mm(store, (F.silu(gu[..., :cfg.ffn]) * gu[..., cfg.ffn:]), p + "feed_forward.w2", a8)
     x = _rms(x, _w(store, "norm.weight"), cfg.norm_eps)
-    return x @ _w(store, "output.weight").t()
+    return _mm(store, x, "output.weight", a8)
 
 
-def forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None) -> torch.Tensor:
+def forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None,
+            act_dtype: str = "bf16") -> torch.Tensor:
+    """``act_dtype="fp8"``: the input of every GEMM whose weight the store holds quantised is
+    quantise-dequantised per row (``quantize_fp8`` / ``dequantize_fp8``: e4m3, one power-of-two
+    scale per row) — what the executor's fp8-activation mode multiplies. The default changes
+    nothing."""
     if cfg.family == "gpt2":
-        return gpt2_forward(cfg, store, tokens)
-    return llama_forward(cfg, store, tokens, router_margins)
+        return gpt2_forward(cfg, store, tokens, act_dtype=act_dtype)
+    return llama_forward(cfg, store, tokens, router_margins, act_dtype=act_dtype)

@@ -30,6 +30,7 @@ def build_dag(cfg: ModelConfig, batch: int = 1, seq: int = 512, cost_model: str 
 
 
 WEIGHT_DTYPES = ("bf16", "fp8", "fp8-experts")
+ACT_DTYPES = ("bf16", "fp8")
 # (op kind, weight key) pairs that read a tensor as a GEMM weight operand
 _GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("attention", "w_o"),
                   ("swiglu_mlp", "w_gate_up"), ("swiglu_mlp", "w_down")}
@@ -60,17 +61,31 @@ def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OP
     return marked
 
 
+def check_act_dtype(act_dtype: str, weight_dtype: str) -> None:
+    """``act_dtype="fp8"`` (e4m3 GEMM inputs, one power-of-two scale per row) exists only over
+    fp8 GEMM weights of a dense model: ``weight_dtype="fp8"``."""
+    if act_dtype not in ACT_DTYPES:
+        raise ValueError(f"act_dtype must be one of {ACT_DTYPES}, got {act_dtype!r}")
+    if act_dtype == "fp8" and weight_dtype != "fp8":
+        raise ValueError(f"act_dtype='fp8' needs weight_dtype='fp8' (the fp8 x fp8 GEMM of dense models), "
+                         f"got weight_dtype={weight_dtype!r}")
+
+
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
-          tp: int = 1, sp: int = 1, weight_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          tp: int = 1, sp: int = 1, weight_dtype: str = "bf16",
+          act_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
     of a dense model are stored as e4m3 with one fp32 scale per output channel
     (:func:`mark_fp8`); not with MoE models, ``tp`` or ``sp``. ``weight_dtype="fp8-experts"``: the
     same storage for the expert weights (``w_gate_up``, ``w_down``) of an MoE model only — router,
-    attention and LM head stay bf16; not with a model without experts, ``tp`` or ``sp``."""
+    attention and LM head stay bf16; not with a model without experts, ``tp`` or ``sp``.
+    ``act_dtype="fp8"`` (checked here, acted on by the executor: the DAG and the stored bytes do
+    not depend on it) needs ``weight_dtype="fp8"``."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
+    check_act_dtype(act_dtype, weight_dtype)
     cfg = get_config(model)
     if weight_dtype == "fp8":
         if cfg.n_experts:

@@ -372,6 +372,103 @@ def linear_w8(x, q, scale, bias=None, act=None, residual=None, alpha=1.0, out=No
     return y
 
 
+W8A8_SPLITS = (1, 2, 4, 8)  # split-K factors of the fp8 x fp8 GEMM (csrc/kernels/gemm_w8a8.hip)
+
+
+def w8a8_configs() -> int:
+    """Number of tile configurations of the fp8 x fp8 GEMM (``linear_w8a8(config=...)``)."""
+    return int(ext().gemm_w8a8_num_configs())
+
+
+def w8a8_workspace_elems(M: int, N: int, K: int) -> int:
+    """fp32 elements of split-K workspace the shape's automatic config needs (0: no K split)."""
+    _, sk = ext().gemm_w8a8_pick(int(M), int(N), int(K))
+    return int(sk) * int(M) * int(N) if sk > 1 else 0
+
+
+def _as_e4m3(t):
+    """A caller's 1-byte buffer (the executor's uint8 scratch) seen as e4m3."""
+    return t if t is None or t.dtype == torch.float8_e4m3fn else t.view(torch.float8_e4m3fn)
+
+
+def _q8_out(q, s, out_q, out_scale):
+    if out_q is not None:
+        _as_e4m3(out_q).view(torch.uint8).copy_(q.reshape(out_q.shape).view(torch.uint8))
+        q = _as_e4m3(out_q)
+    if out_scale is not None:
+        out_scale.copy_(s)
+        s = out_scale
+    return q, s
+
+
+def quantize_rows_fp8(x, out_q=None, out_scale=None):
+    """bf16 activation rows ``x`` [M, K] (rows may be strided) -> ``(q, scale)``: e4m3 [M, K] and
+    one fp32 power-of-two scale per ROW, exactly :func:`quantize_fp8` of ``x`` (byte for byte,
+    up to the sign of a zero). GPU: one launch of quant_rows.hip, which allocates nothing when
+    ``out_q`` (1-byte elements, contiguous) and ``out_scale`` are given. CPU tensors run
+    :func:`quantize_fp8`."""
+    if _gpu(x):
+        q, s = ext().quantize_rows_fp8(x, _as_e4m3(out_q), out_scale)
+        return q.view(x.shape), s
+    q, s = quantize_fp8(x.reshape(-1, x.shape[-1]))
+    q, s = _q8_out(q, s, out_q, out_scale)
+    return q.view(x.shape), s
+
+
+def _norm_q8(x, w, b, eps, residual, sum_out, out_q, out_scale, rms):
+    if _gpu(x):
+        q, s, sm = ext().norm_q8(x, w, b, float(eps), residual, rms, sum_out, _as_e4m3(out_q), out_scale)
+        q = q.view(x.shape)
+        return (q, s, sm.view(x.shape)) if residual is not None else (q, s)
+    r = rmsnorm(x, w, eps, residual=residual, sum_out=sum_out) if rms \
+        else layernorm(x, w, b, eps, residual=residual, sum_out=sum_out)
+    y, sm = r if residual is not None else (r, None)
+    q, s = quantize_rows_fp8(y, out_q, out_scale)
+    return (q, s, sm) if residual is not None else (q, s)
+
+
+def layernorm_q8(x, w, b, eps=1e-5, residual=None, sum_out=None, out_q=None, out_scale=None):
+    """:func:`layernorm` emitting its output as quantised rows: ``(q, scale)`` bitwise what
+    ``quantize_rows_fp8(layernorm(...))`` gives (the bf16-ROUNDED normalised value is what gets
+    quantised), in ONE launch on GPU. With ``residual`` returns ``(q, scale, x + residual)``
+    (``sum_out`` as in :func:`layernorm`). CPU tensors run the two-step composition."""
+    return _norm_q8(x, w, b, eps, residual, sum_out, out_q, out_scale, False)
+
+
+def rmsnorm_q8(x, w, eps=1e-5, residual=None, sum_out=None, out_q=None, out_scale=None):
+    """:func:`rmsnorm` emitting quantised rows; see :func:`layernorm_q8`."""
+    return _norm_q8(x, w, None, eps, residual, sum_out, out_q, out_scale, True)
+
+
+def linear_w8a8(xq, xscale, q, scale, bias=None, act=None, residual=None, alpha=1.0, out=None, config=None,
+                workspace=None):
+    """``act(alpha * xscale[m] * scale[n] * sum_k xq[m][k] * q[n][k] + bias[n]) + residual`` with
+    BOTH operands fp8: ``xq`` e4m3 [M, K] with fp32 row scales ``xscale`` [M]
+    (:func:`quantize_rows_fp8`), ``q`` e4m3 [N, K] with fp32 channel scales ``scale`` [N]
+    (any positive values), K contiguous, K % 16 == 0, fp32 accumulation, bf16 output. GPU: one
+    HIP kernel on the block-scaled fp8 MFMA (gemm_w8a8.hip; neutral block scales, both scales in
+    the epilogue). ``act="swiglu"``, ``config``, ``workspace`` and a strided ``out`` as
+    :func:`linear_w8` (``config`` < :func:`w8a8_configs`, splits ``W8A8_SPLITS``). CPU tensors
+    run :func:`ref_linear` on the two dequantised operands in fp32."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if q.dtype != torch.float8_e4m3fn or xq.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"linear_w8a8: both operands must be float8_e4m3fn, got {xq.dtype} and {q.dtype}")
+    if _gpu(xq):
+        n_out = q.shape[0] // 2 if a == SWIGLU else q.shape[0]
+        cfg, sk = (-1, 0) if config is None else (tuple(config) if isinstance(config, (tuple, list)) else (config, 1))
+        y = ext().gemm_w8a8(xq, xscale, q, scale, bias, residual, a, float(alpha), out, int(cfg), int(sk),
+                            _stream_pol(q.shape[0], q.shape[1]) & 6, workspace)
+        return y.view(xq.shape[:-1] + (n_out,)) if out is None else out
+    if xq.shape[-1] % 16:
+        raise ValueError(f"linear_w8a8: K must be a multiple of 16, got {xq.shape[-1]}")
+    xd = dequantize_fp8(xq.reshape(-1, xq.shape[-1]), xscale, torch.float32).reshape(xq.shape)
+    y = ref_linear(xd, dequantize_fp8(q, scale, torch.float32), bias, act, residual, alpha).to(torch.bfloat16)
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
 def derive_norm_gemm(w, ln_w, ln_b=None, bias=None):
     """Fold a norm's affine into the following GEMM: returns (W' = W * ln_w, colsum(W') in
     fp32, bias' = bias + W @ ln_b). W' is rounded to bf16 BEFORE the column sums, so the

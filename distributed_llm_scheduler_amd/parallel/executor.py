@@ -185,7 +185,7 @@ class DAGExecutor:
                  model_cfg=None, use_graph: bool = True, pg=None, seed: int = 1234, autotune: bool = True,
                  trace: bool = False, debug: bool = False, model_name: Optional[str] = None,
                  input_parts: Optional[Dict[str, List[str]]] = None,
-                 requests: Optional[Dict[str, Tuple[str, int, int]]] = None):
+                 requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16"):
         self.tasks = {t.id: t for t in tasks}
         # the model whose per-model GEMM choices (ops/gemm_tuning.json model_overrides) this
         # executor's launches use: set around each of its steps, captures and refinements, so
@@ -231,6 +231,16 @@ class DAGExecutor:
         # statistics, no post-norm, RoPE stand-alone, none of the one-launch fused blocks.
         self._q_names = {sp.name for g in store.groups.values() for sp in g.tensors if sp.quant}
         self._w8_ws: Optional[torch.Tensor] = None  # split-K partial slabs of the fp8-weight GEMMs
+        # fp8 activations (runtime.plan act_dtype="fp8"): the input rows of every GEMM on an fp8
+        # weight are quantised per row (by the norm in front of it, or by one quantiser launch)
+        # into per-rank scratch and multiplied by ops.linear_w8a8; GEMMs on bf16 weights are untouched
+        if act_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"act_dtype must be 'bf16' or 'fp8', got {act_dtype!r}")
+        if act_dtype == "fp8" and not self._q_names:
+            raise ValueError("act_dtype='fp8' needs fp8 GEMM weights (weight_dtype='fp8')")
+        self._a8 = act_dtype == "fp8"
+        self._a8_q: Optional[torch.Tensor] = None  # quantised rows (uint8) of the current GEMM input
+        self._a8_s: Optional[torch.Tensor] = None  # their fp32 row scales
         # GPU, host-image refills: a transformed weight's bytes are written back into a private
         # copy of its group's pinned image, so every later refill restores the TRANSFORMED
         # weight and its (colsum, bias') stay valid wherever the group lands (no re-derivation
@@ -1218,7 +1228,17 @@ class DAGExecutor:
             # scale), the fp8-weight GEMM, then RoPE stand-alone on the natural q/k layout
             if stats_out is not None:
                 raise RuntimeError(f"{w_name}: an fp8-weight GEMM emits no row statistics")
-            if norm is not None:
+            xq = None
+            if norm is not None and self._a8:
+                # fp8 activations: the norm emits the quantised rows and their scales itself
+                oq, osc = self._a8_rows(x.shape[0], x.shape[-1])
+                if norm.op.kind == "layernorm":
+                    xq = ops.layernorm_q8(x, self._w(norm.op.weights["w"]), self._w(norm.op.weights["b"]),
+                                          norm.op.attrs.get("eps", 1e-5), out_q=oq, out_scale=osc)
+                else:
+                    xq = ops.rmsnorm_q8(x, self._w(norm.op.weights["w"]), norm.op.attrs.get("eps", 1e-5),
+                                        out_q=oq, out_scale=osc)
+            elif norm is not None:
                 xn = self._scratch("norm", x.shape)
                 if norm.op.kind == "layernorm":
                     ops.layernorm(x, self._w(norm.op.weights["w"]), self._w(norm.op.weights["b"]),
@@ -1226,7 +1246,7 @@ class DAGExecutor:
                 else:
                     ops.rmsnorm(x, self._w(norm.op.weights["w"]), norm.op.attrs.get("eps", 1e-5), out=xn)
                 x = xn
-            y = self._linear(x, w_name, b_name, act=act, residual=residual, out=out, interleave=sw)
+            y = self._linear(x, w_name, b_name, act=act, residual=residual, out=out, interleave=sw, xq=xq)
             if rope is not None:
                 cos, sin, S, D, cols = rope
                 nh, nkv, _ = rope_perm
@@ -1267,10 +1287,11 @@ class DAGExecutor:
         return ops.linear(x, W, bias, act=act, residual=residual, out=out, rope=rope, stats_out=stats_out)
 
     def _linear(self, x, w_name, b_name=None, act=None, residual=None, out=None, stats_out=None, post_norm=None,
-                interleave: bool = False):
+                interleave: bool = False, xq=None):
         """A plain GEMM node on a resident weight, by the weight's storage: bf16 ->
         ``ops.linear``; fp8 -> ``ops.linear_w8`` (no row statistics, no post-norm: the planners
-        give such groups neither)."""
+        give such groups neither), or with fp8 activations ``ops.linear_w8a8`` on ``xq`` = the
+        input's (e4m3 rows, row scales) — from the norm in front, else one quantiser launch here."""
         W = self._w(w_name)
         bias = self._w(b_name) if b_name else None
         if W.dtype != torch.float8_e4m3fn:
@@ -1282,16 +1303,38 @@ class DAGExecutor:
         if interleave:
             bias = self._prep_w8(w_name, W, scale, bias)
         ws = None
+        M = x.numel() // x.shape[-1]
+        if self._a8 and xq is None:
+            x2 = x.reshape(M, x.shape[-1])
+            xq = ops.quantize_rows_fp8(x2, *self._a8_rows(M, x2.shape[-1]))
         if self.gpu:
             # split-K partial slabs: one buffer per rank, grown in eager steps only (kernels of
             # one rank run in order on its stream, so consecutive GEMMs may share it)
-            need = ops.w8_workspace_elems(x.numel() // x.shape[-1], W.shape[0], W.shape[1])
+            need = (ops.w8a8_workspace_elems if self._a8 else ops.w8_workspace_elems)(M, W.shape[0], W.shape[1])
             if need and (self._w8_ws is None or self._w8_ws.numel() < need):
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("fp8-weight GEMM workspace must be allocated before hipGraph capture")
                 self._w8_ws = torch.empty(need, dtype=torch.float32, device=self.device)
             ws = self._w8_ws if need else None
+        if self._a8:
+            return ops.linear_w8a8(xq[0].reshape(M, -1), xq[1], W, scale, bias, act=act, residual=residual, out=out,
+                                   workspace=ws)
         return ops.linear_w8(x, W, scale, bias, act=act, residual=residual, out=out, workspace=ws)
+
+    def _a8_rows(self, M: int, K: int):
+        """Per-rank scratch for one GEMM input's quantised rows: (uint8 [M, K], fp32 [M]) — one
+        buffer pair, grown in eager steps only (a rank's kernels run in order on its stream, so
+        consecutive GEMMs share it). The CPU backend lets the ops allocate."""
+        if not self.gpu:
+            return None, None
+        if self._a8_q is None or self._a8_q.numel() < M * K or self._a8_s.numel() < M:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fp8 activation scratch must be allocated before hipGraph capture")
+            self._a8_q = torch.empty(max(M * K, self._a8_q.numel() if self._a8_q is not None else 0),
+                                     dtype=torch.uint8, device=self.device)
+            self._a8_s = torch.empty(max(M, self._a8_s.numel() if self._a8_s is not None else 0),
+                                     dtype=torch.float32, device=self.device)
+        return self._a8_q[:M * K].view(M, K), self._a8_s[:M]
 
     def _prep_w8(self, w_name: str, q: torch.Tensor, scale: torch.Tensor, bias):
         """SwiGLU row interleave of an fp8 [gate; up] weight, IN PLACE once per fill: the e4m3

@@ -66,7 +66,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          batch: int = 1, seq: int = 512, cost_model: str = "bytes", fuse: bool = True,
          node_speeds: Optional[Sequence[float]] = None, link_bw_gbps: float = 153.0,
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
-         residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16") -> Plan:
+         residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
+         act_dtype: str = "bf16") -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -107,6 +108,11 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     weights of an MoE model only (router, attention and LM head stay bf16); raises ``ValueError``
     with a model without experts, ``tp > 1`` or ``sp > 1``.
 
+    ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` only; anything else raises ``ValueError``):
+    the input rows of every GEMM on an fp8 weight are quantised to e4m3 with one power-of-two
+    scale per row and multiplied on the fp8 MFMA (``ops.linear_w8a8``); the DAG, the bytes and
+    the placement are those of ``weight_dtype="fp8"``.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -123,6 +129,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
         args["sp"] = sp
     if weight_dtype != "bf16":  # (only when not the default: plans saved before it still resume)
         args["weight_dtype"] = weight_dtype
+    if act_dtype != "bf16":  # (validated by registry.build below)
+        args["act_dtype"] = act_dtype
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -137,7 +145,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
             for j, k in enumerate(members):
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
-                                        sp=sp, weight_dtype=weight_dtype)
+                                        sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
     nodes = [Node(f"gpu{r}", caps_gb[r], (node_speeds[r] if node_speeds else 1.0), device=r) for r in range(world)]
     node_rank = {n.id: r for r, n in enumerate(nodes)}
@@ -251,6 +259,8 @@ def _resume(path: str, args: Dict, sched):
     mismatch = {k: (saved.get(k), v) for k, v in args.items() if k not in ("fuse",) and saved.get(k) != v}
     if saved.get("weight_dtype", "bf16") != args.get("weight_dtype", "bf16"):  # (absent: the default)
         mismatch["weight_dtype"] = (saved.get("weight_dtype", "bf16"), args.get("weight_dtype", "bf16"))
+    if saved.get("act_dtype", "bf16") != args.get("act_dtype", "bf16"):
+        mismatch["act_dtype"] = (saved.get("act_dtype", "bf16"), args.get("act_dtype", "bf16"))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -585,4 +595,4 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
     # per-model GEMM choices by the canonical preset name (aliases such as "mixtral" resolve to it)
     return DAGExecutor(p.tasks, p.programs[rank], store or make_store(p), device, model_cfg=p.cfg,
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
-                       input_parts=p.input_parts, requests=p.requests)
+                       input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"))
