@@ -7,10 +7,12 @@ step and kernel launches of the captured step. One JSON line per run.
     python benchmarks/bench_w8_step.py --model mixtral-8x7b --weight-dtype fp8-experts [--cap 65.4]
 
     python benchmarks/bench_w8_step.py --model llama3-8b --modes bf16,fp8,fp8+a8
+    python benchmarks/bench_w8_step.py --model llama3-8b --cap 5.993 --modes fp8+a8,mxfp4+a8
 
 ``--weight-dtype D`` runs bf16 next to D (``--modes`` lists the modes explicitly). Mode ``fp8+a8``
 is fp8 weights with fp8 activations (``act_dtype="fp8"``: the fp8 x fp8 GEMM); ``--act-dtype fp8``
-adds it to the default modes.
+adds it to the default modes. Mode ``mxfp4+a8`` is MXFP4 weights with fp8 activations (the W4A8
+GEMM; MXFP4 weights have no other mode).
 """
 from __future__ import annotations
 
@@ -68,7 +70,7 @@ def main():
     ap.add_argument("--act-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: also run <--weight-dtype>+a8 (fp8 activations; with --weight-dtype fp8)")
     ap.add_argument("--modes", default=None,
-                    help="comma-separated modes: a weight dtype, or fp8+a8 (default: bf16,<--weight-dtype>)")
+                    help="comma-separated modes: a weight dtype, fp8+a8 or mxfp4+a8 (default: bf16,<--weight-dtype>)")
     a = ap.parse_args()
     if a.modes is None:
         a.modes = "bf16," + a.weight_dtype + ("," + a.weight_dtype + "+a8" if a.act_dtype == "fp8" else "")

@@ -195,6 +195,37 @@ int gemm_w8a8_max_splitk(int cfg, int K);
 size_t gemm_w8a8_workspace_bytes(int M, int N, int splitk);
 void launch_gemm_w8a8(const GemmW8A8Args& a, hipStream_t s);
 
+// W4A8 GEMM (gemm_w4a8.hip): C = act(alpha * xscale[m] * sum_k Aq[m][k] * W[n][k] + bias[n]) + R
+// with e4m3 activation rows (one fp32 scale per row) and OCP MXFP4 weights: Wq [N][K/2] bytes, two
+// e2m1 per byte (even k in the low nibble), Ws [N][K/32] e8m0 block scales, on the block-scaled
+// MFMA (16x16x128, fp4 x fp8). K % 32 == 0, any M, N (N % 32 == 0 for SwiGLU).
+struct GemmW4A8Args {
+  const void* Aq;  // e4m3 [M][lda]
+  int lda;
+  const float* xscale;  // fp32 [M], positive
+  const void* Wq;       // e2m1 pairs [N][ldw bytes]
+  int ldw;
+  const void* Ws;  // e8m0 [N][lds], codes 0..254
+  int lds;
+  void* C;  // bf16 [M][ldc] (SwiGLU: N/2 columns)
+  int ldc;
+  const void* bias;  // bf16 [N] or nullptr
+  const void* R;     // bf16 [M][ldr] or nullptr
+  int ldr;
+  int M, N, K;
+  int act;  // DlsAct
+  float alpha;
+  int config;        // 0..gemm_w4a8_num_configs()-1
+  int splitk;        // >= 1; > 1: fp32 partial slabs in `workspace`, summed in a fixed order
+  float* workspace;  // gemm_w4a8_workspace_bytes() when splitk > 1
+  int store_pol;     // as GemmW8Args::store_pol
+};
+int gemm_w4a8_num_configs();
+void gemm_w4a8_pick(int M, int N, int K, int* cfg, int* splitk);
+int gemm_w4a8_max_splitk(int cfg, int K);
+size_t gemm_w4a8_workspace_bytes(int M, int N, int splitk);
+void launch_gemm_w4a8(const GemmW4A8Args& a, hipStream_t s);
+
 // Per-row e4m3 quantisation (quant_rows.hip): q[m][k] = rne(x[m][k] / scale[m]) with scale[m] the
 // smallest power of two with amax_m / scale[m] <= 448 (all-zero row: 1). x bf16 [M][ldx],
 // q e4m3 [M][ldq], K % 8 == 0.

@@ -390,6 +390,93 @@ at::Tensor gemm_w8a8(const at::Tensor& xq_in, const at::Tensor& xscale, const at
   return c;
 }
 
+// W4A8 GEMM (gemm_w4a8.hip): xq e4m3 [M][K] with fp32 row scales, wq uint8 [N][K/2] (two e2m1 per
+// byte) with ws uint8 [N][K/32] e8m0 block scales. config / splitk / workspace as gemm_w8.
+at::Tensor gemm_w4a8(const at::Tensor& xq_in, const at::Tensor& xscale, const at::Tensor& wq,
+                     const at::Tensor& ws_in, const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& residual, int64_t act, double alpha,
+                     const c10::optional<at::Tensor>& out, int64_t config, int64_t splitk, int64_t store_pol,
+                     const c10::optional<at::Tensor>& workspace) {
+  TORCH_CHECK(xq_in.is_cuda() && xq_in.scalar_type() == at::kFloat8_e4m3fn, "xq must be a float8_e4m3fn GPU tensor");
+  at::Tensor a = as2d(xq_in);
+  TORCH_CHECK(wq.is_cuda() && wq.device() == a.device() && wq.scalar_type() == at::kByte,
+              "W must be a uint8 tensor (two e2m1 per byte) on xq's GPU");
+  TORCH_CHECK(wq.dim() == 2, "W must be 2-D");
+  const int64_t M = a.size(0), K = a.size(1), N = wq.size(0);
+  TORCH_CHECK(K % 32 == 0, "the MXFP4 GEMM needs K % 32 == 0, got K = ", K);
+  TORCH_CHECK(wq.size(1) == K / 2, "W must be [N][K/2] bytes with K = ", K, ", got ", wq.sizes());
+  TORCH_CHECK(a.stride(1) == 1 && a.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              "xq must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(wq.stride(1) == 1 && wq.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+              "W must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(xscale.is_cuda() && xscale.device() == a.device() && xscale.scalar_type() == at::kFloat &&
+                  xscale.is_contiguous() && xscale.numel() == M,
+              "xscale must be a contiguous fp32 [M] tensor on xq's GPU");
+  TORCH_CHECK(ws_in.is_cuda() && ws_in.device() == a.device() && ws_in.scalar_type() == at::kByte &&
+                  ws_in.dim() == 2 && ws_in.size(0) == N && ws_in.size(1) == K / 32 && ws_in.stride(1) == 1,
+              "the block scales must be a uint8 [N][K/32] tensor with contiguous rows on xq's GPU");
+  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
+  const bool swiglu = act == kActSwiglu;
+  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
+  const int64_t NO = swiglu ? N / 2 : N;
+  const auto bf = a.options().dtype(at::kBFloat16);
+  at::Tensor c;
+  if (out.has_value()) {
+    c = as2d(*out);
+    check_bf16(c, "out");
+    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
+                "out must be [M][N_out] with contiguous rows");
+  } else {
+    c = at::empty({M, NO}, bf);
+  }
+  const void* bptr = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
+    bptr = bias->data_ptr();
+  }
+  const void* rptr = nullptr;
+  int ldr = 0;
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
+    rptr = r.data_ptr();
+    ldr = (int)r.stride(0);
+  }
+  if (M == 0 || N == 0) return c;
+  int cfg = (int)config, sk = (int)splitk;
+  if (cfg < 0 || sk <= 0) {
+    int acfg, ask;
+    gemm_w4a8_pick((int)M, (int)N, (int)K, &acfg, &ask);
+    if (cfg < 0) {
+      cfg = acfg;
+      if (sk <= 0) sk = ask;
+    } else if (sk <= 0) {
+      sk = 1;
+    }
+  }
+  TORCH_CHECK(cfg < gemm_w4a8_num_configs(), "unknown MXFP4 GEMM config ", cfg);
+  sk = std::min(sk, gemm_w4a8_max_splitk(cfg, (int)K));
+  at::Tensor ws;
+  if (sk > 1) {
+    const int64_t need = (int64_t)gemm_w4a8_workspace_bytes((int)M, (int)N, sk) / 4;
+    if (workspace.has_value()) {
+      ws = *workspace;
+      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
+                      ws.is_contiguous() && ws.numel() >= need,
+                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
+    } else {
+      ws = at::empty({need}, a.options().dtype(at::kFloat));
+    }
+  }
+  GemmW4A8Args g{a.data_ptr(), (int)a.stride(0), xscale.data_ptr<float>(), wq.data_ptr(), (int)wq.stride(0),
+                 ws_in.data_ptr(), (int)ws_in.stride(0), c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K,
+                 (int)act, (float)alpha, cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+  launch_gemm_w4a8(g, cur_stream());
+  return c;
+}
+
 // (q, scale) outputs of the row quantisers: e4m3 [M][K] contiguous rows and fp32 [M], the
 // caller's (checked) or fresh ones
 std::pair<at::Tensor, at::Tensor> q8_outputs(const at::Tensor& like, int64_t M, int64_t K,
@@ -1238,6 +1325,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_w8a8_pick", [](int M, int N, int K) {
     int c, s;
     gemm_w8a8_pick(M, N, K, &c, &s);
+    return std::make_pair(c, s);
+  });
+  m.def("gemm_w4a8", &gemm_w4a8, py::arg("xq"), py::arg("xscale"), py::arg("wq"), py::arg("ws"),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0,
+        py::arg("out") = py::none(), py::arg("config") = -1, py::arg("splitk") = 0, py::arg("store_pol") = 0,
+        py::arg("workspace") = py::none());
+  m.def("gemm_w4a8_num_configs", &gemm_w4a8_num_configs);
+  m.def("gemm_w4a8_pick", [](int M, int N, int K) {
+    int c, s;
+    gemm_w4a8_pick(M, N, K, &c, &s);
     return std::make_pair(c, s);
   });
   m.def("quantize_rows_fp8", &quantize_rows_fp8, py::arg("x"), py::arg("out_q") = py::none(),

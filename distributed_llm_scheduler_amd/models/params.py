@@ -32,6 +32,9 @@ class TensorSpec:
     # fp8 weight storage (registry.build weight_dtype="fp8"): a GEMM weight [N, K] kept as e4m3
     # bytes [N][K] followed (256-B aligned) by one fp32 scale per output channel [N]
     quant: bool = False
+    # storage format of a quantised tensor: "fp8" (above) or "mxfp4" (weight_dtype="mxfp4"): OCP
+    # MXFP4, N*K/2 bytes of e2m1 pairs followed (256-B aligned) by N*K/32 e8m0 block-scale bytes
+    qfmt: str = "fp8"
 
     @property
     def numel(self) -> int:
@@ -47,12 +50,16 @@ class ParamGroup:
     tensors: List[TensorSpec] = field(default_factory=list)
 
     def nbytes(self, dtype_bytes: int = 2) -> int:
-        return sum(t.numel + 4 * t.shape[0] if t.quant else t.numel * dtype_bytes for t in self.tensors)
+        return sum(sum(quant_parts(t)[::2]) if t.quant else t.numel * dtype_bytes for t in self.tensors)
 
 
 def quant_parts(spec: TensorSpec) -> Tuple[int, int, int]:
-    """A quantised tensor inside its group: (bytes of the e4m3 part, byte offset of the scales
-    from the tensor's start, bytes of the fp32 scales)."""
+    """A quantised tensor inside its group: (bytes of the data part, byte offset of the scales
+    from the tensor's start, bytes of the scales). fp8: N*K e4m3 bytes and N fp32 scales; mxfp4:
+    N*K/2 bytes of e2m1 pairs and N*K/32 e8m0 bytes."""
+    if spec.qfmt == "mxfp4":
+        qb = spec.numel // 2
+        return qb, _align(qb), spec.numel // MX_BLOCK
     qb = spec.numel
     return qb, _align(qb), 4 * spec.shape[0]
 
@@ -82,6 +89,57 @@ def quantize_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 def dequantize_fp8(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
     """``q[n][k] * scale[n]`` (exact in bf16 for power-of-two scales)."""
     return (q.float() * scale.float().reshape(-1, *([1] * (q.dim() - 1)))).to(dtype)
+
+
+MX_BLOCK = 32  # elements per e8m0 block scale (OCP MX)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """OCP MXFP4 quantisation of ``w`` [N, K] (K % 32 == 0): every 32 consecutive elements of a
+    row share one e8m0 scale ``2^e``, the smallest with ``amax_block / 2^e <= 6`` (e clamped to
+    [-127, 127]; an all-zero block: 2^0), and become e2m1 codes (bit 3 the sign, codes 0..7 =
+    0, 0.5, 1, 1.5, 2, 3, 4, 6) of ``w / 2^e`` rounded to nearest, ties to even, saturating at
+    +-6. Every e2m1 value times a power of two is a bf16 value, so :func:`dequantize_mxfp4` of
+    the result is exactly a bf16 tensor. Runs on ``w``'s device. Returns ``(q uint8 [N, K/2],
+    s uint8 [N, K/32])``: element k of a row is the low (k even) / high (k odd) nibble of byte
+    k/2, and scale code c means 2^(c - 127) (255 is never written)."""
+    w2 = w.detach().reshape(w.shape[0], -1)
+    N, K = w2.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"quantize_mxfp4: K must be a multiple of {MX_BLOCK}, got {K}")
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    s = torch.empty((N, K // MX_BLOCK), dtype=torch.uint8, device=w.device)
+    step = max(1, (1 << 26) // max(K, 1))  # rows per pass: the fp32 temporaries stay small
+    for r in range(0, N, step):
+        wf = w2[r:r + step].float().reshape(-1, K // MX_BLOCK, MX_BLOCK)
+        amax = wf.abs().amax(dim=2)
+        m, ex = torch.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1); 6 = 0.75 * 2^3
+        e = torch.where(m <= 0.75, ex - 3, ex - 2).clamp_(-127, 127)
+        e = torch.where(amax > 0, e, torch.zeros_like(e))
+        s[r:r + step] = (e + 127).to(torch.uint8)
+        x = torch.ldexp(wf, -e[:, :, None])
+        a = x.abs().clamp_(max=6.0)
+        # round half to even on the grid: steps of 0.5 below 2, of 1 below 4, of 2 above
+        v = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+        code = torch.where(v < 2, v * 2, torch.where(v < 4, v + 2, v / 2 + 4)).to(torch.uint8)
+        code = (code | (torch.signbit(x).to(torch.uint8) << 3)).reshape(-1, K)
+        q[r:r + step] = code[:, 0::2] | (code[:, 1::2] << 4)
+    return q, s
+
+
+def dequantize_mxfp4(q: torch.Tensor, s: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """``e2m1(q[n][k]) * 2^(s[n][k/32] - 127)`` as ``dtype`` [N, K] (exact in bf16)."""
+    N, K = q.shape[0], q.shape[1] * 2
+    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=q.device)
+    out = torch.empty((N, K), dtype=dtype, device=q.device)
+    step = max(1, (1 << 26) // max(K, 1))
+    for r in range(0, N, step):
+        qq = q[r:r + step]
+        codes = torch.stack((qq & 15, qq >> 4), dim=2).reshape(-1, K // MX_BLOCK, MX_BLOCK)
+        e = s[r:r + step].to(torch.int32) - 127
+        out[r:r + step] = torch.ldexp(lut[codes.long()], e[:, :, None]).reshape(-1, K).to(dtype)
+    return out
 
 
 def _seed(name: str, base: int) -> int:
@@ -180,15 +238,17 @@ class ParamStore:
         return t
 
     def _quantize(self, name: str, t: torch.Tensor) -> torch.Tensor:
-        q, scale = quantize_fp8(t)
+        mx = self._spec(name).qfmt == "mxfp4"
+        q, scale = quantize_mxfp4(t) if mx else quantize_fp8(t)
         self._quant[name] = (q.pin_memory(), scale.pin_memory()) if self.pin else (q, scale)
-        return dequantize_fp8(q, scale, self.dtype)
+        return (dequantize_mxfp4(q, scale, self.dtype).reshape(t.shape) if mx
+                else dequantize_fp8(q, scale, self.dtype))
 
     def quantized(self, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``(q e4m3 [N, K], scale fp32 [N])`` of a quantised tensor (``tensor(name)`` is their
-        product)."""
+        """``(q e4m3 [N, K], scale fp32 [N])`` of an fp8 tensor, ``(q uint8 [N, K/2], s uint8
+        [N, K/32])`` of an mxfp4 one (``tensor(name)`` is the dequantised product)."""
         if not self._spec(name).quant:
-            raise KeyError(f"{name} is not stored as fp8")
+            raise KeyError(f"{name} is not stored quantised")
         if name not in self._quant:
             self.tensor(name)
         return self._quant[name]
@@ -197,11 +257,16 @@ class ParamStore:
         sp = self._specs.get(name)
         return sp is not None and sp.quant
 
+    def quant_format(self, name: str) -> Optional[str]:
+        """``"fp8"`` / ``"mxfp4"`` for a quantised tensor, ``None`` for a bf16 one."""
+        sp = self._specs.get(name)
+        return sp.qfmt if sp is not None and sp.quant else None
+
     def _spec(self, name: str) -> TensorSpec:
         return self._specs[name]
 
     def fill(self, name: str, out: torch.Tensor, scale_out: Optional[torch.Tensor] = None) -> None:
-        """Write tensor ``name`` into ``out`` (an HBM arena view); a quantised tensor's e4m3
+        """Write tensor ``name`` into ``out`` (an HBM arena view); a quantised tensor's data
         part into ``out`` and its scales into ``scale_out``."""
         spec = self._spec(name)
         if spec.quant:
@@ -209,7 +274,7 @@ class ParamStore:
                 # bf16 scratch in HBM, quantised there: still no host copy
                 full = torch.empty(spec.shape, dtype=self.dtype, device=out.device)
                 fill_on_device(spec, full, self.seed)
-                q, scale = quantize_fp8(full)
+                q, scale = quantize_mxfp4(full) if spec.qfmt == "mxfp4" else quantize_fp8(full)
                 out.copy_(q)
                 scale_out.copy_(scale)
             else:
@@ -236,7 +301,7 @@ class ParamStore:
                     q, scale = self.quantized(spec.name)
                     qb, s_off, sb = quant_parts(spec)
                     img[off:off + qb].copy_(q.contiguous().view(-1).view(torch.uint8))
-                    img[off + s_off:off + s_off + sb].copy_(scale.contiguous().view(torch.uint8))
+                    img[off + s_off:off + s_off + sb].copy_(scale.contiguous().view(-1).view(torch.uint8))
                     continue
                 t = self.tensor(spec.name).contiguous()
                 img[off:off + t.numel() * t.element_size()].copy_(t.view(-1).view(torch.uint8))
@@ -258,7 +323,7 @@ class ParamStore:
         if tuple(value.shape) != tuple(spec.shape):
             raise ValueError(f"{name}: expected shape {spec.shape}, got {tuple(value.shape)}")
         t = value.detach().to("cpu", self.dtype).contiguous()
-        if spec.quant:  # stored as fp8: what tensor() returns is what the kernels multiply
+        if spec.quant:  # stored quantised: what tensor() returns is what the kernels multiply
             t = self._quantize(name, t)
         self._host[name] = t.pin_memory() if self.pin else t
         self._images = {k: v for k, v in self._images.items()
@@ -275,14 +340,15 @@ def _align(n: int) -> int:
 def group_layout(group: ParamGroup, dtype_bytes: int = 2):
     """Byte layout of a parameter group inside the HBM parameter arena: every tensor
     starts 256-B aligned (16-B vector loads, cache-line aligned rows). A quantised tensor
-    (``spec.quant``) takes N*K bytes of e4m3 and, 256-B aligned behind them, 4*N bytes of
-    scales (:func:`quant_parts`).
+    (``spec.quant``) takes its data bytes and, 256-B aligned behind them, its scale bytes
+    (:func:`quant_parts`: fp8 N*K and 4*N, mxfp4 N*K/2 and N*K/32).
     Returns ``(total_bytes, [(spec, byte_offset), ...])``."""
     off, out = 0, []
     for spec in group.tensors:
         out.append((spec, off))
         if spec.quant:
-            off += _align(spec.numel) + _align(4 * spec.shape[0])
+            qb, s_off, sb = quant_parts(spec)
+            off += s_off + _align(sb)
         else:
             off += _align(spec.numel * dtype_bytes)
     return off, out

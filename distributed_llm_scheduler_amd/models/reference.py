@@ -134,7 +134,8 @@ def forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_ma
             act_dtype: str = "bf16") -> torch.Tensor:
     """``act_dtype="fp8"``: the input of every GEMM whose weight the store holds quantised is
     quantise-dequantised per row (``quantize_fp8`` / ``dequantize_fp8``: e4m3, one power-of-two
-    scale per row) — what the executor's fp8-activation mode multiplies. The default changes
+    scale per row) — what the executor's fp8-activation mode multiplies, over fp8 and mxfp4
+    weights alike (``store.tensor`` is the dequantised weight in either format). The default changes
     nothing."""
     if cfg.family == "gpt2":
         return gpt2_forward(cfg, store, tokens, act_dtype=act_dtype)

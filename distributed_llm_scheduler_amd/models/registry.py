@@ -5,7 +5,7 @@ from typing import Dict, List, Tuple
 
 from ..core.task import Task
 from .config import ModelConfig, get_config
-from .params import ParamGroup
+from .params import MX_BLOCK, ParamGroup
 
 
 def param_groups(cfg: ModelConfig) -> Dict[str, ParamGroup]:
@@ -30,6 +30,9 @@ def build_dag(cfg: ModelConfig, batch: int = 1, seq: int = 512, cost_model: str 
 
 
 WEIGHT_DTYPES = ("bf16", "fp8", "fp8-experts")
+# block-scaled (OCP MX) weight storage, accepted next to WEIGHT_DTYPES: "mxfp4" marks the tensors
+# "fp8" marks (dense models) and needs act_dtype="fp8"
+MX_WEIGHT_DTYPES = ("mxfp4",)
 ACT_DTYPES = ("bf16", "fp8")
 # (op kind, weight key) pairs that read a tensor as a GEMM weight operand
 _GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("attention", "w_o"),
@@ -39,8 +42,9 @@ _GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("a
 _EXPERT_OPERANDS = {("moe_expert", "w_gate_up"), ("moe_expert", "w_down")}
 
 
-def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OPERANDS) -> List[str]:
-    """Mark for fp8 storage (``TensorSpec.quant``) every tensor that EVERY reader reads as one
+def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OPERANDS,
+             fmt: str = "fp8") -> List[str]:
+    """Mark for quantised storage in format ``fmt`` ("fp8", or "mxfp4": ``TensorSpec.qfmt``) (``TensorSpec.quant``) every tensor that EVERY reader reads as one
     of ``operands`` — (op kind, weight key) pairs: by default the GEMM weight operands of a
     dense model, ``_EXPERT_OPERANDS`` for the experts of an MoE model. Embedding tables, norm
     gains, biases and a weight an embedding also gathers from (GPT-2's tied ``wte``) stay bf16.
@@ -56,19 +60,27 @@ def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OP
     for g in groups.values():
         for sp in g.tensors:
             if sp.name in gemm and sp.name not in other and len(sp.shape) == 2 and sp.parent is None:
+                if fmt == "mxfp4" and sp.shape[1] % MX_BLOCK:
+                    raise ValueError(f"weight_dtype='mxfp4': {sp.name} has K = {sp.shape[1]}, not a multiple of "
+                                     f"{MX_BLOCK} (one e8m0 scale per {MX_BLOCK} elements)")
                 sp.quant = True
+                sp.qfmt = fmt
                 marked.append(sp.name)
     return marked
 
 
 def check_act_dtype(act_dtype: str, weight_dtype: str) -> None:
     """``act_dtype="fp8"`` (e4m3 GEMM inputs, one power-of-two scale per row) exists only over
-    fp8 GEMM weights of a dense model: ``weight_dtype="fp8"``."""
+    quantised GEMM weights of a dense model: ``weight_dtype="fp8"`` (the W8A8 kernel) or
+    ``"mxfp4"`` (the W4A8 kernel, which is the only MXFP4 GEMM: ``"mxfp4"`` needs ``"fp8"``)."""
     if act_dtype not in ACT_DTYPES:
         raise ValueError(f"act_dtype must be one of {ACT_DTYPES}, got {act_dtype!r}")
-    if act_dtype == "fp8" and weight_dtype != "fp8":
-        raise ValueError(f"act_dtype='fp8' needs weight_dtype='fp8' (the fp8 x fp8 GEMM of dense models), "
-                         f"got weight_dtype={weight_dtype!r}")
+    if act_dtype == "fp8" and weight_dtype not in ("fp8", "mxfp4"):
+        raise ValueError(f"act_dtype='fp8' needs weight_dtype='fp8' or 'mxfp4' (the fp8 x fp8 and MXFP4 x fp8 "
+                         f"GEMMs of dense models), got weight_dtype={weight_dtype!r}")
+    if weight_dtype == "mxfp4" and act_dtype != "fp8":
+        raise ValueError(f"weight_dtype='mxfp4' needs act_dtype='fp8': there is one MXFP4 kernel, W4A8 (e4m3 "
+                         f"activation rows on the block-scaled MFMA), got act_dtype={act_dtype!r}")
 
 
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
@@ -82,9 +94,12 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     same storage for the expert weights (``w_gate_up``, ``w_down``) of an MoE model only — router,
     attention and LM head stay bf16; not with a model without experts, ``tp`` or ``sp``.
     ``act_dtype="fp8"`` (checked here, acted on by the executor: the DAG and the stored bytes do
-    not depend on it) needs ``weight_dtype="fp8"``."""
-    if weight_dtype not in WEIGHT_DTYPES:
-        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
+    not depend on it) needs ``weight_dtype="fp8"`` or ``"mxfp4"``. ``weight_dtype="mxfp4"``: the
+    tensors ``"fp8"`` marks, stored as OCP MXFP4 (e2m1 pairs + one e8m0 scale per 32 elements of K,
+    0.53 bytes per element); dense models only, no ``tp`` / ``sp``, every marked K a multiple of
+    32, and ``act_dtype="fp8"`` (the one kernel is W4A8)."""
+    if weight_dtype not in WEIGHT_DTYPES + MX_WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES + MX_WEIGHT_DTYPES}, got {weight_dtype!r}")
     check_act_dtype(act_dtype, weight_dtype)
     cfg = get_config(model)
     if weight_dtype == "fp8":
@@ -93,6 +108,11 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
                              "their expert weights as fp8 (attention, router and LM head stay bf16)")
         if tp > 1 or sp > 1:
             raise ValueError("weight_dtype='fp8' does not combine with tensor or sequence parallelism (tp, sp > 1)")
+    if weight_dtype == "mxfp4":
+        if cfg.n_experts:
+            raise ValueError("weight_dtype='mxfp4' does not cover MoE models (dense models only)")
+        if tp > 1 or sp > 1:
+            raise ValueError("weight_dtype='mxfp4' does not combine with tensor or sequence parallelism (tp, sp > 1)")
     if weight_dtype == "fp8-experts":
         if not cfg.n_experts:
             raise ValueError(f"weight_dtype='fp8-experts' needs an MoE model; {model} has no experts "
@@ -116,4 +136,6 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         mark_fp8(tasks, groups)
     elif weight_dtype == "fp8-experts":
         mark_fp8(tasks, groups, _EXPERT_OPERANDS)
+    elif weight_dtype == "mxfp4":
+        mark_fp8(tasks, groups, fmt="mxfp4")
     return tasks, groups, cfg

@@ -469,6 +469,74 @@ def linear_w8a8(xq, xscale, q, scale, bias=None, act=None, residual=None, alpha=
     return y
 
 
+def quantize_mxfp4(w):
+    """bf16 GEMM weight [N, K] (K % 32 == 0) -> ``(q, s)`` in OCP MXFP4: ``q`` uint8 [N, K/2],
+    element k of a row in the low (k even) / high (k odd) nibble of byte k/2 as e2m1 (bit 3 the
+    sign, codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6), and ``s`` uint8 [N, K/32] e8m0, code c =
+    2^(c - 127), the smallest power of two with ``amax_block / 2^e <= 6`` (an all-zero block:
+    127); round-to-nearest-even, saturating at +-6. ``W[n][k] ~= e2m1(q[n][k]) * 2^(s[n][k/32] -
+    127)``, exactly a bf16 value. Runs on ``w``'s device."""
+    from ..models.params import quantize_mxfp4 as _q
+    return _q(w)
+
+
+def dequantize_mxfp4(q, s, dtype=torch.bfloat16):
+    """``e2m1(q[n][k]) * 2^(s[n][k/32] - 127)`` as ``dtype`` [N, K] (exact in bf16)."""
+    from ..models.params import dequantize_mxfp4 as _d
+    return _d(q, s, dtype)
+
+
+W4A8_SPLITS = (1, 2, 4, 8)  # split-K factors of the MXFP4 x fp8 GEMM (csrc/kernels/gemm_w4a8.hip)
+
+
+def w4a8_configs() -> int:
+    """Number of tile configurations of the MXFP4 x fp8 GEMM (``linear_w4a8(config=...)``)."""
+    return int(ext().gemm_w4a8_num_configs())
+
+
+def w4a8_workspace_elems(M: int, N: int, K: int) -> int:
+    """fp32 elements of split-K workspace the shape's automatic config needs (0: no K split)."""
+    _, sk = ext().gemm_w4a8_pick(int(M), int(N), int(K))
+    return int(sk) * int(M) * int(N) if sk > 1 else 0
+
+
+def linear_w4a8(xq, xscale, q, s, bias=None, act=None, residual=None, alpha=1.0, out=None, config=None,
+                workspace=None):
+    """``act(alpha * xscale[m] * sum_k xq[m][k] * W[n][k] + bias[n]) + residual`` with fp8
+    activations and an MXFP4 weight: ``xq`` e4m3 [M, K] with fp32 row scales ``xscale`` [M]
+    (:func:`quantize_rows_fp8`), ``W[n][k] = e2m1(q[n][k]) * 2^(s[n][k/32] - 127)`` in the layout
+    of :func:`quantize_mxfp4` (``q`` uint8 [N, K/2], ``s`` uint8 [N, K/32], any code 0..254),
+    K % 32 == 0, fp32 accumulation, bf16 output. GPU: one HIP kernel on the block-scaled MFMA
+    with an fp4 and an fp8 operand (gemm_w4a8.hip; the hardware applies the block scales, the
+    row scale is applied in the epilogue). ``act="swiglu"`` (rows of ``q`` and ``s`` interleaved
+    together), ``config``, ``workspace`` and a strided ``out`` as :func:`linear_w8` (``config``
+    < :func:`w4a8_configs`, splits ``W4A8_SPLITS``). CPU tensors run :func:`ref_linear` on the
+    two dequantised operands in fp32."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if xq.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"linear_w4a8: the activations must be float8_e4m3fn, got {xq.dtype}")
+    if q.dtype != torch.uint8 or s.dtype != torch.uint8:
+        raise TypeError(f"linear_w4a8: the MXFP4 weight and its block scales must be uint8, got {q.dtype} and {s.dtype}")
+    K = xq.shape[-1]
+    if K % 32:
+        raise ValueError(f"linear_w4a8: K must be a multiple of 32, got {K}")
+    if q.dim() != 2 or q.shape[1] != K // 2 or tuple(s.shape) != (q.shape[0], K // 32):
+        raise ValueError(f"linear_w4a8: expected q [N, {K // 2}] and s [N, {K // 32}], got {tuple(q.shape)} and "
+                         f"{tuple(s.shape)}")
+    if _gpu(xq):
+        n_out = q.shape[0] // 2 if a == SWIGLU else q.shape[0]
+        cfg, sk = (-1, 0) if config is None else (tuple(config) if isinstance(config, (tuple, list)) else (config, 1))
+        y = ext().gemm_w4a8(xq, xscale, q, s, bias, residual, a, float(alpha), out, int(cfg), int(sk),
+                            _stream_pol(q.shape[0], K) & 6, workspace)
+        return y.view(xq.shape[:-1] + (n_out,)) if out is None else out
+    xd = dequantize_fp8(xq.reshape(-1, K), xscale, torch.float32).reshape(xq.shape)
+    y = ref_linear(xd, dequantize_mxfp4(q, s, torch.float32), bias, act, residual, alpha).to(torch.bfloat16)
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
 def derive_norm_gemm(w, ln_w, ln_b=None, bias=None):
     """Fold a norm's affine into the following GEMM: returns (W' = W * ln_w, colsum(W') in
     fp32, bias' = bias + W @ ln_b). W' is rounded to bf16 BEFORE the column sums, so the

@@ -126,7 +126,8 @@ FOLD_MAX_K = 1024  # fold a preceding norm into the GEMM only up to this K (see 
 # widest norm input whose statistics a producer GEMM hands over (beyond it: a norm kernel)
 HANDOFF_MAX_K = int(os.environ.get("DLS_HANDOFF_MAX_K", str(FOLD_MAX_K)))
 GUARD_BYTES, GUARD_VALUE = 4096, 0xA5  # debug-mode canary after each arena slab
-SCALE_SUFFIX = "@scale"  # view name of an fp8 weight's per-row fp32 scales (DAGExecutor._views_at)
+# view name of a quantised weight's scales (DAGExecutor._views_at): fp8 per-row fp32, mxfp4 e8m0 blocks
+SCALE_SUFFIX = "@scale"
 # producer GEMMs emit row statistics for the next folded norm (GPU); DLS_STATS_HANDOFF=0 disables
 STATS_HANDOFF = os.environ.get("DLS_STATS_HANDOFF", "1") != "0"
 # the embedding kernel hands layer 0's folded norm its rows' statistics too (0: that norm's GEMM
@@ -230,6 +231,11 @@ class DAGExecutor:
         # Their GEMMs run ops.linear_w8 with the norm as its own kernel: no folded norm, no row
         # statistics, no post-norm, RoPE stand-alone, none of the one-launch fused blocks.
         self._q_names = {sp.name for g in store.groups.values() for sp in g.tensors if sp.quant}
+        # MXFP4 weight storage (registry weight_dtype="mxfp4"): e2m1 pairs + e8m0 block scales. Their
+        # GEMMs dispatch on the stored format (_linear) to ops.linear_w4a8, the one mxfp4 kernel
+        mx = sorted(sp.name for g in store.groups.values() for sp in g.tensors if sp.quant and sp.qfmt == "mxfp4")
+        if mx and act_dtype != "fp8":
+            raise ValueError(f"mxfp4 weights ({mx[0]}, ...) need act_dtype='fp8': there is one MXFP4 GEMM, W4A8")
         self._w8_ws: Optional[torch.Tensor] = None  # split-K partial slabs of the fp8-weight GEMMs
         # fp8 activations (runtime.plan act_dtype="fp8"): the input rows of every GEMM on an fp8
         # weight are quantised per row (by the norm in front of it, or by one quantiser launch)
@@ -881,9 +887,14 @@ class DAGExecutor:
         views = {}
         for spec, sub in layout:
             n = spec.numel
-            if spec.quant:  # e4m3 bytes, then (256-B aligned) one fp32 scale per row
+            if spec.quant:  # data bytes, then (256-B aligned) the scales
                 qb, s_off, sb = quant_parts(spec)
                 b = off + sub
+                if spec.qfmt == "mxfp4":  # e2m1 pairs [N][K/2], e8m0 block scales [N][K/32]
+                    N = spec.shape[0]
+                    views[spec.name] = self.param_slab[b:b + qb].view(N, qb // N)
+                    views[spec.name + SCALE_SUFFIX] = self.param_slab[b + s_off:b + s_off + sb].view(N, sb // N)
+                    continue
                 views[spec.name] = self.param_slab[b:b + qb].view(torch.float8_e4m3fn).view(spec.shape)
                 views[spec.name + SCALE_SUFFIX] = self.param_slab[b + s_off:b + s_off + sb].view(torch.float32)
                 continue
@@ -1212,7 +1223,7 @@ class DAGExecutor:
         img[sub:sub + nb].copy_(W.reshape(-1).view(torch.uint8))  # blocking D2H
         if scale is not None:  # an fp8 weight: its per-row scales moved with the rows
             _, s_off, sb = quant_parts(self.store._spec(w_name))
-            img[sub + s_off:sub + s_off + sb].copy_(scale.view(torch.uint8))
+            img[sub + s_off:sub + s_off + sb].copy_(scale.reshape(-1).view(torch.uint8))
         self._derived_named[w_name] = d
 
     def _gemm(self, x, w_name, b_name, norm: Optional[Task], act=None, residual=None, out=None, rope=None,
@@ -1294,11 +1305,12 @@ class DAGExecutor:
         input's (e4m3 rows, row scales) — from the norm in front, else one quantiser launch here."""
         W = self._w(w_name)
         bias = self._w(b_name) if b_name else None
-        if W.dtype != torch.float8_e4m3fn:
+        mx = W.dtype == torch.uint8  # the stored format decides: an mxfp4 weight's e2m1 pairs
+        if W.dtype != torch.float8_e4m3fn and not mx:
             return ops.linear(x, W, bias, act=act, residual=residual, out=out, stats_out=stats_out,
                               post_norm=post_norm)
         if stats_out is not None or post_norm is not None:
-            raise RuntimeError(f"{w_name}: an fp8-weight GEMM takes no row statistics / post-norm")
+            raise RuntimeError(f"{w_name}: a quantised-weight GEMM takes no row statistics / post-norm")
         scale = self._w(w_name + SCALE_SUFFIX)
         if interleave:
             bias = self._prep_w8(w_name, W, scale, bias)
@@ -1310,12 +1322,16 @@ class DAGExecutor:
         if self.gpu:
             # split-K partial slabs: one buffer per rank, grown in eager steps only (kernels of
             # one rank run in order on its stream, so consecutive GEMMs may share it)
-            need = (ops.w8a8_workspace_elems if self._a8 else ops.w8_workspace_elems)(M, W.shape[0], W.shape[1])
+            need = (ops.w4a8_workspace_elems(M, W.shape[0], x.shape[-1]) if mx else
+                    (ops.w8a8_workspace_elems if self._a8 else ops.w8_workspace_elems)(M, W.shape[0], W.shape[1]))
             if need and (self._w8_ws is None or self._w8_ws.numel() < need):
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("fp8-weight GEMM workspace must be allocated before hipGraph capture")
                 self._w8_ws = torch.empty(need, dtype=torch.float32, device=self.device)
             ws = self._w8_ws if need else None
+        if mx:
+            return ops.linear_w4a8(xq[0].reshape(M, -1), xq[1], W, scale, bias, act=act, residual=residual, out=out,
+                                   workspace=ws)
         if self._a8:
             return ops.linear_w8a8(xq[0].reshape(M, -1), xq[1], W, scale, bias, act=act, residual=residual, out=out,
                                    workspace=ws)
@@ -1337,8 +1353,9 @@ class DAGExecutor:
         return self._a8_q[:M * K].view(M, K), self._a8_s[:M]
 
     def _prep_w8(self, w_name: str, q: torch.Tensor, scale: torch.Tensor, bias):
-        """SwiGLU row interleave of an fp8 [gate; up] weight, IN PLACE once per fill: the e4m3
-        rows and their scales together (and the bias with them). Persisted into the group's
+        """SwiGLU row interleave of a quantised [gate; up] weight, IN PLACE once per fill: the data
+        rows and their scales (fp8: one per row; mxfp4: a row of block scales) together (and the
+        bias with them). Persisted into the group's
         host image like a bf16 transform, so refills carry the interleaved bytes."""
         named = self._derived_named.get(w_name)
         if named is not None:

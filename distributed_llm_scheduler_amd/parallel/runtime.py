@@ -106,12 +106,15 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     about half the parameter bytes under the same cap. Raises ``ValueError`` with an MoE model,
     ``tp > 1`` or ``sp > 1``. ``weight_dtype="fp8-experts"``: the same storage for the expert
     weights of an MoE model only (router, attention and LM head stay bf16); raises ``ValueError``
-    with a model without experts, ``tp > 1`` or ``sp > 1``.
+    with a model without experts, ``tp > 1`` or ``sp > 1``. ``weight_dtype="mxfp4"``: the tensors
+    ``"fp8"`` marks, stored as OCP MXFP4 (e2m1 pairs and one e8m0 scale per 32 elements of K:
+    0.53 bytes per element); raises ``ValueError`` with an MoE model, ``tp > 1``, ``sp > 1``, a
+    marked K that is no multiple of 32, or ``act_dtype != "fp8"`` (the one kernel is W4A8).
 
-    ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` only; anything else raises ``ValueError``):
-    the input rows of every GEMM on an fp8 weight are quantised to e4m3 with one power-of-two
-    scale per row and multiplied on the fp8 MFMA (``ops.linear_w8a8``); the DAG, the bytes and
-    the placement are those of ``weight_dtype="fp8"``.
+    ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` or ``"mxfp4"`` only; anything else raises
+    ``ValueError``): the input rows of every GEMM on a quantised weight are quantised to e4m3 with
+    one power-of-two scale per row and multiplied on the block-scaled MFMA (``ops.linear_w8a8`` /
+    ``ops.linear_w4a8``); the DAG, the bytes and the placement are those of the ``weight_dtype``.
 
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
