@@ -1,39 +1,55 @@
 // In-kernel phase timing of one LDS-DMA GEMM config (diagnostic executable): compiles
-// csrc/kernels/gemm_glds_impl.h (configs 34, 24, 27, 17, 25, 22) into this translation unit with DLS_STAMP recording
-// s_memrealtime (100 MHz) per workgroup at: tile start, after the main loop, after the output
-// image is in LDS, after the store pass.
+// csrc/kernels/gemm_glds_impl.h (configs 34, 13, 24, 27, 17, 45, 25, 22) into this translation unit
+// with DLS_STAMP recording s_memrealtime (100 MHz) per workgroup at: tile start, after the main
+// loop, after the K-group sum, after the output image is in LDS, after the store pass.
 //
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Icsrc/kernels benchmarks/gemm_stamps.hip -o gpubin/gemm_stamps
-//   gpubin/gemm_stamps <cfg> <M> <N> <K>
+// The epilogue mode attaches the operands a model step attaches (none: a bare GEMM):
+//   res     bias + residual + stats_out            (GPT-2 out-proj, fc2)
+//   lngelu  bias + ln_colsum + ext_stats, GeLU     (fc1: folded LayerNorm, external statistics)
+//   ln      bias + ln_colsum + ext_stats           (QKV, LM head)
+// The operands are written by earlier launches, as in a step. The stamps in the middle of the
+// epilogue wait for the stamping wave's LDS traffic only (a vmcnt(0) there would drain operand
+// requests that are meant to be in flight across the phase boundary).
+//
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -Icsrc/kernels \
+//         benchmarks/gemm_stamps.hip -o gpubin/gemm_stamps
+//   gpubin/gemm_stamps <cfg> <M> <N> <K> [none|res|lngelu|ln]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
-__device__ unsigned long long g_stamps[4096 * 4];
+constexpr int kMaxBlocks = 4096, kSlots = 8;
+__device__ unsigned long long g_stamps[kMaxBlocks * kSlots];
 #define DLS_STAMP(k)                                                                     \
-  if (threadIdx.x == 0 && blockIdx.x < 4096) {                                           \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                          \
-    g_stamps[blockIdx.x * 4 + (k)] = __builtin_amdgcn_s_memrealtime();                   \
+  if (threadIdx.x == 0 && blockIdx.x < kMaxBlocks) {                                     \
+    if ((k) == 0 || (k) == 3) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                              \
+    g_stamps[blockIdx.x * kSlots + (k)] = __builtin_amdgcn_s_memrealtime();              \
   }
-#include "../csrc/kernels/gemm_glds_impl.h"
+#include "gemm_glds_impl.h"
 DLS_GLDS_DEFINE(34)
+DLS_GLDS_DEFINE(13)
 DLS_GLDS_DEFINE(24)
 DLS_GLDS_DEFINE(27)
 DLS_GLDS_DEFINE(17)
+DLS_GLDS_DEFINE(45)
 DLS_GLDS_DEFINE(25)
 DLS_GLDS_DEFINE(22)
 // splitk = 1 only: the split-K reduce launcher of the library is stubbed out below
-static bool launch_gemm_glds_local(const GemmArgs& a, int cfg, int splitk) {
+static bool launch_gemm_glds_local(const GemmArgs& a, int cfg, const float* colsum, int ln_mode) {
   switch (cfg) {
-    case 24: return glds_launch_cfg24(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
-    case 27: return glds_launch_cfg27(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
-    case 17: return glds_launch_cfg17(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
-    case 25: return glds_launch_cfg25(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
-    case 22: return glds_launch_cfg22(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
-    default: return glds_launch_cfg34(a, splitk, nullptr, 0, nullptr, 0, 1e-5f, nullptr, false);
+    case 13: return glds_launch_cfg13(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 24: return glds_launch_cfg24(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 27: return glds_launch_cfg27(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 17: return glds_launch_cfg17(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 45: return glds_launch_cfg45(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 25: return glds_launch_cfg25(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    case 22: return glds_launch_cfg22(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
+    default: return glds_launch_cfg34(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
   }
 }
 bool glds_reduce(const GemmArgs&, int, float*, hipStream_t, const float*, int, float, const int*, const Epi&) { return false; }
@@ -41,48 +57,84 @@ bool glds_reduce(const GemmArgs&, int, float*, hipStream_t, const float*, int, f
 int main(int argc, char** argv) {
   const int cfg = argc > 1 ? atoi(argv[1]) : 34;
   const int M = argc > 2 ? atoi(argv[2]) : 512, N = argc > 3 ? atoi(argv[3]) : 32768, K = argc > 4 ? atoi(argv[4]) : 768;
-  std::vector<unsigned short> h((size_t)std::max(M, N) * K);
+  const char* mode = argc > 5 ? argv[5] : "none";
+  const bool res = !strcmp(mode, "res"), ln = !strcmp(mode, "ln") || !strcmp(mode, "lngelu");
+  if (!res && !ln && strcmp(mode, "none")) {
+    fprintf(stderr, "epilogue mode: none, res, lngelu or ln\n");
+    return 2;
+  }
+  std::vector<unsigned short> h(std::max({(size_t)M * K, (size_t)N * K, (size_t)M * N}));
   for (size_t i = 0; i < h.size(); ++i) h[i] = 0x3c00 + (unsigned short)(rand() & 0x3ff);  // bf16 in [1, 2)
-  void *A, *W, *C;
+  void *A, *W, *C, *B, *R;
+  float *colsum, *ext, *stats;
   hipMalloc(&A, (size_t)M * K * 2);
   hipMalloc(&W, (size_t)N * K * 2);
   hipMalloc(&C, (size_t)M * N * 2);
+  hipMalloc(&B, (size_t)N * 2);
+  hipMalloc(&R, (size_t)M * N * 2);
+  hipMalloc(&colsum, (size_t)N * 4);
+  hipMalloc(&ext, (size_t)M * 2 * 4);
+  hipMalloc(&stats, (size_t)M * 2 * 4);
   hipMemcpy(A, h.data(), (size_t)M * K * 2, hipMemcpyHostToDevice);
   hipMemcpy(W, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice);
+  hipMemcpy(B, h.data(), (size_t)N * 2, hipMemcpyHostToDevice);
+  hipMemcpy(R, h.data(), (size_t)M * N * 2, hipMemcpyHostToDevice);
+  // statistics of rows whose values have mean 1.5 and mean square 2.5 (a positive variance)
+  std::vector<float> f((size_t)std::max(2 * M, N));
+  for (int i = 0; i < M; ++i) {
+    f[2 * i] = 1.5f * K;
+    f[2 * i + 1] = 2.5f * K;
+  }
+  hipMemcpy(ext, f.data(), (size_t)M * 2 * 4, hipMemcpyHostToDevice);
+  for (int i = 0; i < N; ++i) f[i] = 1.5f * K;
+  hipMemcpy(colsum, f.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+  hipMemset(stats, 0, (size_t)M * 2 * 4);
   GemmArgs g{};
   g.A = A; g.lda = K; g.W = W; g.ldw = K; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.alpha = 1.f;
   g.config = cfg;
+  if (res) {
+    g.bias = B; g.R = R; g.ldr = N; g.stats_out = stats;
+  } else if (ln) {
+    g.bias = B; g.ext_stats = ext;
+    g.act = !strcmp(mode, "lngelu") ? ACT_GELU_TANH : ACT_NONE;
+  }
+  const float* cs = ln ? colsum : nullptr;
+  const int ln_mode = ln ? 1 : 0;
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   hipMemset(C, 0, (size_t)M * N * 2);
-  for (int i = 0; i < 5; ++i) launch_gemm_glds_local(g, cfg, 1);
-  hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), std::vector<unsigned long long>(4096 * 4, 0).data(), 4096 * 4 * 8);
+  for (int i = 0; i < 5; ++i) launch_gemm_glds_local(g, cfg, cs, ln_mode);
+  hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), std::vector<unsigned long long>(kMaxBlocks * kSlots, 0).data(),
+                    kMaxBlocks * kSlots * 8);
   hipEventRecord(e0);
-  launch_gemm_glds_local(g, cfg, 1);
+  launch_gemm_glds_local(g, cfg, cs, ln_mode);
   hipEventRecord(e1);
-  hipEventSynchronize(e1);
+  if (hipEventSynchronize(e1) != hipSuccess) {
+    fprintf(stderr, "launch failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
   float ms = 0;
   hipEventElapsedTime(&ms, e0, e1);
-  std::vector<unsigned long long> st(4096 * 4);
+  std::vector<unsigned long long> st(kMaxBlocks * kSlots);
   hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamps), st.size() * 8);
-  int nb = 0;
-  for (int b = 0; b < 4096; ++b)
-    if (st[b * 4]) nb = b + 1;
   unsigned long long t0 = ~0ull, tend = 0;
-  std::vector<double> d01, d12, d23, start, end;
-  for (int b = 0; b < nb; ++b) {
-    const unsigned long long* s = &st[b * 4];
+  for (int b = 0; b < kMaxBlocks; ++b) {
+    const unsigned long long* s = &st[b * kSlots];
     if (!s[0]) continue;
     t0 = std::min(t0, s[0]);
     tend = std::max(tend, s[3]);
   }
-  for (int b = 0; b < nb; ++b) {
-    const unsigned long long* s = &st[b * 4];
+  // phases: 0 -> 1 main loop, 1 -> 7 K-group sum, 7 -> 2 image, 2 -> 3 store
+  std::vector<double> d_main, d_sum, d_img, d_store, d_epi, start, end;
+  for (int b = 0; b < kMaxBlocks; ++b) {
+    const unsigned long long* s = &st[b * kSlots];
     if (!s[0]) continue;
-    d01.push_back((s[1] - s[0]) * 0.01);
-    d12.push_back((s[2] - s[1]) * 0.01);
-    d23.push_back((s[3] - s[2]) * 0.01);
+    d_main.push_back((s[1] - s[0]) * 0.01);
+    d_sum.push_back((s[7] - s[1]) * 0.01);
+    d_img.push_back((s[2] - s[7]) * 0.01);
+    d_store.push_back((s[3] - s[2]) * 0.01);
+    d_epi.push_back((s[3] - s[1]) * 0.01);
     start.push_back((s[0] - t0) * 0.01);
     end.push_back((s[3] - t0) * 0.01);
   }
@@ -90,12 +142,19 @@ int main(int argc, char** argv) {
     std::sort(v.begin(), v.end());
     return v.empty() ? 0.0 : v[(size_t)(p * (v.size() - 1))];
   };
-  printf("cfg %d  M %d N %d K %d: event %.2f us; blocks %zu; first-start -> last-end %.2f us\n", cfg, M, N, K,
-         ms * 1e3, d01.size(), (tend - t0) * 0.01);
+  auto mean = [](const std::vector<double>& v) {
+    double s = 0;
+    for (double x : v) s += x;
+    return v.empty() ? 0.0 : s / v.size();
+  };
+  printf("cfg %d  M %d N %d K %d  epilogue %s: event %.2f us; blocks %zu; first-start -> last-end %.2f us\n", cfg, M,
+         N, K, mode, ms * 1e3, d_main.size(), (tend - t0) * 0.01);
   printf("  start offset   min %.2f med %.2f max %.2f us\n", q(start, 0), q(start, .5), q(start, 1));
-  printf("  main loop      min %.2f med %.2f max %.2f us\n", q(d01, 0), q(d01, .5), q(d01, 1));
-  printf("  image to LDS   min %.2f med %.2f max %.2f us\n", q(d12, 0), q(d12, .5), q(d12, 1));
-  printf("  store pass     min %.2f med %.2f max %.2f us\n", q(d23, 0), q(d23, .5), q(d23, 1));
+  printf("  main loop      min %.2f med %.2f max %.2f mean %.2f us\n", q(d_main, 0), q(d_main, .5), q(d_main, 1), mean(d_main));
+  printf("  K-group sum    min %.2f med %.2f max %.2f mean %.2f us\n", q(d_sum, 0), q(d_sum, .5), q(d_sum, 1), mean(d_sum));
+  printf("  image to LDS   min %.2f med %.2f max %.2f mean %.2f us\n", q(d_img, 0), q(d_img, .5), q(d_img, 1), mean(d_img));
+  printf("  store pass     min %.2f med %.2f max %.2f mean %.2f us\n", q(d_store, 0), q(d_store, .5), q(d_store, 1), mean(d_store));
+  printf("  after the loop min %.2f med %.2f max %.2f mean %.2f us\n", q(d_epi, 0), q(d_epi, .5), q(d_epi, 1), mean(d_epi));
   printf("  end offset     min %.2f med %.2f max %.2f us\n", q(end, 0), q(end, .5), q(end, 1));
   return 0;
 }

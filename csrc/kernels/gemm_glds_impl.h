@@ -27,7 +27,9 @@
 #include "gemm_glds_cfgs.h"
 
 // In-kernel phase stamps for diagnostic builds (benchmarks/gemm_stamps.hip defines it before
-// including this file); empty in the library.
+// including this file); empty in the library. glds_tile stamps 0 tile start, 1 after the main
+// loop, 7 after the K-group sum, 2 after the output image is in LDS, 3 after the store pass
+// (4-6 belong to gemm_fused.hip).
 #ifndef DLS_STAMP
 #define DLS_STAMP(k)
 #endif
@@ -52,6 +54,23 @@ __device__ __forceinline__ void wait_tiles(int ahead) {
   }
 }
 __device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
+// Workgroup barrier of the epilogue's LDS hand-offs: the wave's own LDS traffic is complete
+// (lgkmcnt(0)) before it arrives. WAIT_LDS_ONLY leaves its global loads in flight — the
+// __syncthreads() fence puts a vmcnt(0) in front of the barrier, which would end the batched
+// epilogue operand requests (Cfg::EPI_BATCH) at the first barrier after them.
+// A value requested earlier is consumed from HERE on: the (empty) statement is its first use,
+// so the compiler's vmcnt wait for the load lands at this point and no arithmetic on the value
+// can be moved up to the request (InstCombine folds an operation on a phi of {constant, load}
+// into the load's block — a wait right behind the request).
+template <class T>
+__device__ __forceinline__ void consume_from_here(T& x) {
+  asm volatile("" : "+v"(x));
+}
+template <bool WAIT_LDS_ONLY>
+__device__ __forceinline__ void epi_barrier() {
+  if constexpr (WAIT_LDS_ONLY) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  else __syncthreads();
+}
 
 // BXS = extra weight (B) stages: 0 -> A and W tiles share STAGES buffers and travel
 // together; >= 1 -> A keeps STAGES buffers (it is L2-resident: short latency) while the COLD
@@ -94,7 +113,15 @@ struct Cfg {
   static_assert(STAGES >= 2 && STAGES <= 8, "stages");
   static_assert(LDS_UNITS * 16 <= 163840, "LDS budget");
   static_assert(KG == 1 || (BXS == 0 && PRIO == 0), "K groups use the joint ring");
-  static_assert(KG == 1 || NW * 64 * FM * FN * 16 <= LDS_UNITS * 16, "K-group reduction must fit the LDS");
+  // one LDS region of NW * FM * FN KiB per K group past the first (all written before ONE barrier)
+  static_assert(KG == 1 || (KG - 1) * NW * 64 * FM * FN * 16 <= LDS_UNITS * 16, "K-group reduction must fit the LDS");
+  // Batched epilogue operand requests (glds_tile): the small wave tiles of the skinny M = 512
+  // GEMMs, whose body is a few us and whose epilogue operands (row statistics, bias, colsum,
+  // residual) otherwise arrive one dependent round trip after another behind barriers. At most
+  // 4 accumulator fragments per lane: the requests' 20-odd destination registers are free there.
+  // The large tiles (128 accumulator registers and more next to their fragment registers) keep
+  // the in-place loads — their epilogue is a small share of a long body.
+  static constexpr bool EPI_BATCH = FM * FN <= 4;
   static_assert(!RING || (BM == 256 && BN == 256 && WM == 2 && WN == 4 && STAGES == 2 && KG == 1 && BXS == 0),
                 "the ring main loop is written for 256x256 tiles, 8 waves as 2 x 4, 8 x 16 KiB slots");
 };
@@ -582,9 +609,127 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
     mainloop_joint<C, GATHER, APOL, WPOL>(smem, A, lda, W, ldw, M, N, m0, n0, kbeg, nk, lane, wave, kgrp, wm, wn, ln_acc, acc,
                                     st_s, st_q, arows);
   DLS_STAMP(1)
-  if constexpr (C::KG > 1) {
+  const int g4 = (lane >> 4) * 4, r16 = lane & 15;
+  // geometry of the staged epilogue's tile image and store pass (see below)
+  constexpr int BNC = C::BN / 8;
+  constexpr int BNP = BNC <= 8 ? 8 : BNC <= 16 ? 16 : BNC <= 32 ? 32 : 64;
+  constexpr int NPASS = (C::BM * BNP + C::T - 1) / C::T;  // store passes of a thread
+  // Batched epilogue operand requests (C::EPI_BATCH). Every global operand of the staged
+  // epilogue is requested HERE, in one batch: after the K loop's final vmcnt(0) (the rings'
+  // counted waits never see these loads, and nothing is live across the K loop — the operand
+  // fragments are dead now), ahead of the K-group sum's barriers, so the L2 / Infinity-Cache
+  // round trips run under the reduction instead of one after another behind the barriers that
+  // follow. Issued before the K loop the same requests cost 2.5 % of the GPT-2 step
+  // (profiles/r3_ab/gpt2_epilogue_prefetch_vs_none.txt). The loads are branch-free per lane (a
+  // guarded load costs a latency each); only uniform conditions branch. They are BUFFER loads:
+  // the descriptor ends with the operand, so a lane past the operand's end gets zeros without a
+  // memory request (as the grouped launches' A rows, mainloop_split) — no clamp arithmetic, one
+  // 32-bit offset per operand and the fragments' strides in the instructions' immediate offsets:
+  // at a 1-2 us epilogue the address VALU of 64-bit clamped pointers was itself measurable.
+  //  * K group 0 (it runs the image pass) asks for ext_stats of its rows and bias / ln_colsum
+  //    of its columns: one 8-B / 16-B load per fragment when the operand is aligned and
+  //    N % 4 == 0 (a fragment's 4 columns are then all inside N or all outside), else one
+  //    clamped scalar per value, each to a register of its own (packing them would wait for
+  //    every load on the spot); values of columns past N are replaced by 0 where consumed;
+  //  * every thread of the store pass asks for the 16-B residual segments it will own there
+  //    (rl / cc depend on tid alone); a segment that straddles N takes the scalar path below.
+  const bool pre_bvec = ((reinterpret_cast<uintptr_t>(bias) & 7) | (N & 3)) == 0;
+  const bool pre_cvec = ((reinterpret_cast<uintptr_t>(ln_colsum) & 15) | (N & 3)) == 0;
+  // (16-B segments as in the store pass: v16 there; 32-bit byte offsets)
+  const bool pre_res = C::EPI_BATCH && R != nullptr && N >= 8 && ((size_t)(M + C::BM) * ldr * 2 < (1ull << 31)) &&
+                       ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2) | reinterpret_cast<uintptr_t>(R) |
+                         ((uintptr_t)ldr * 2)) & 15) == 0;
+  u32x2 pre_bv[C::FN];       // pre_bvec: the fragment's 4 bf16
+  uint32_t pre_bs[C::FN][4];  // else: one bf16 (low half) per register
+  u32x4 pre_cs[C::FN];       // fp32 bits
+  u32x2 pre_st[C::FM];       // fp32 bits of (sum, sum of squares)
+  u32x4 pre_r[NPASS];
+  // (no initial values: a register written on the paths that request nothing would, on the
+  // structurised control flow, be written behind a pending load of the other path — a wait.
+  // Every read below sits under the condition its request sat under.)
+  auto request_operands = [&]() {
+    constexpr int kRaw = 0x00020000;  // raw buffer, 32-bit data
+    if (kgrp == 0) {
+      if (ln_mode != 0 && !LN) {
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ep.ext_stats), 0, M * 8, kRaw);
+        const int vo = (m0 + wm * C::WTM + r16) * 8;  // (rows past M: zeros, never stored)
+#pragma unroll
+        for (int i = 0; i < C::FM; ++i) pre_st[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, vo + i * 128, 0, 0);
+      }
+      const int c0 = n0 + wn * C::WTN + g4;  // the lane's first column; fragment j: + 16 j
+      if (bias) {
+        if (pre_bvec) {
+          const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(bias), 0, N * 2, kRaw);
+#pragma unroll
+          for (int j = 0; j < C::FN; ++j) pre_bv[j] = __builtin_amdgcn_raw_buffer_load_b64(rs, c0 * 2 + j * 32, 0, 0);
+        } else {
+          const unsigned short* b16 = reinterpret_cast<const unsigned short*>(bias);
+#pragma unroll
+          for (int j = 0; j < C::FN; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pre_bs[j][e] = b16[min(c0 + j * 16 + e, N - 1)];
+        }
+      }
+      if (ln_mode != 0) {
+        if (pre_cvec) {
+          const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ln_colsum), 0, N * 4, kRaw);
+#pragma unroll
+          for (int j = 0; j < C::FN; ++j) pre_cs[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, c0 * 4 + j * 64, 0, 0);
+        } else {
+          const uint32_t* c32 = reinterpret_cast<const uint32_t*>(ln_colsum);
+#pragma unroll
+          for (int j = 0; j < C::FN; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pre_cs[j][e] = c32[min(c0 + j * 16 + e, N - 1)];
+        }
+      }
+    }
+    if (pre_res) {
+      // the descriptor ends with row M-1's N-th column: a segment of a row past M reads zeros;
+      // one inside M that reaches past N reads (and nobody uses) what follows in R's buffer
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(R), 0, (int)(((size_t)(M - 1) * ldr + N) * 2), kRaw);
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p) {
+        const int q = tid + p * C::T;
+        if (q < C::BM * BNP)  // (wave-uniform: BM * BNP is a multiple of 64)
+          pre_r[p] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((m0 + q / BNP) * ldr + n0 + (q % BNP) * 8) * 2, 0, 0);
+      }
+    }
+  };
+  if constexpr (C::EPI_BATCH) {
+    // (a split-K slice stores a partial tile, and SwiGLU has its own epilogue: neither reaches
+    // the staged epilogue; the in-launch combine asks once it knows it is the last arriver)
+    if (part == nullptr && act != ACT_SWIGLU) request_operands();
+  }
+  if constexpr (C::KG > 2) {
+    // sum the K groups' accumulators into group 0 in ONE round: group g >= 1 writes its
+    // fragments to its own region of the (now free) staging buffers, one barrier, and group 0
+    // adds the regions in the order 1, 2, .., KG-1 — the same sum, bit for bit, as a write /
+    // barrier / add / barrier round per group. The staged epilogue's own barrier (or the norm
+    // statistics' / the split-K combine's) separates group 0's reads from the next LDS writes.
+    constexpr int REG = C::NW * C::FM * C::FN * 64;  // f32x4 records per group
+    epi_barrier<C::EPI_BATCH>();  // every wave is done with the staging buffers
+    f32x4* red = reinterpret_cast<f32x4*>(smem);
+    if (kgrp != 0) {
+#pragma unroll
+      for (int i = 0; i < C::FM; ++i)
+#pragma unroll
+        for (int j = 0; j < C::FN; ++j)
+          red[(kgrp - 1) * REG + ((i * C::FN + j) * C::NW + wq) * 64 + lane] = acc[i][j];
+    }
+    epi_barrier<C::EPI_BATCH>();
+    if (kgrp == 0) {
+#pragma unroll
+      for (int g2 = 1; g2 < C::KG; ++g2)
+#pragma unroll
+        for (int i = 0; i < C::FM; ++i)
+#pragma unroll
+          for (int j = 0; j < C::FN; ++j)
+            acc[i][j] += red[(g2 - 1) * REG + ((i * C::FN + j) * C::NW + wq) * 64 + lane];
+    }
+  } else if constexpr (C::KG > 1) {
     // sum the K groups' accumulators into group 0 (lane-contiguous 16-B records)
-    __syncthreads();
+    epi_barrier<C::EPI_BATCH>();
     f32x4* red = reinterpret_cast<f32x4*>(smem);
     for (int g2 = 1; g2 < C::KG; ++g2) {
       if (kgrp == g2) {
@@ -593,18 +738,18 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
 #pragma unroll
           for (int j = 0; j < C::FN; ++j) red[((i * C::FN + j) * C::NW + wq) * 64 + lane] = acc[i][j];
       }
-      __syncthreads();
+      epi_barrier<C::EPI_BATCH>();
       if (kgrp == 0) {
 #pragma unroll
         for (int i = 0; i < C::FM; ++i)
 #pragma unroll
           for (int j = 0; j < C::FN; ++j) acc[i][j] += red[((i * C::FN + j) * C::NW + wq) * 64 + lane];
       }
-      __syncthreads();
+      epi_barrier<C::EPI_BATCH>();
     }
   }
 
-  const int g4 = (lane >> 4) * 4, r16 = lane & 15;
+  DLS_STAMP(7)
   if (part != nullptr && ep.tile_sem != nullptr) {
     // In-launch split-K combine (cdna_hip_programming.md §projection GEMM item 2, sc1 form):
     // every K slice stores its fp32 tile WRITE-THROUGH (sc1) into its slab, drains, and one
@@ -643,6 +788,9 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
     __syncthreads();
     const bool last = flag[0] != 0;
     if (!last) return;  // block-uniform
+    if constexpr (C::EPI_BATCH) {
+      if (act != ACT_SWIGLU) request_operands();  // the last arriver runs the staged epilogue
+    }
     if (kgrp == 0) {
       const int nsl = kslice_count(K, kslice);
       for (int s2 = 0; s2 < nsl; ++s2) {
@@ -707,8 +855,19 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
       const float inv_k = 1.0f / (float)K;
 #pragma unroll
       for (int i = 0; i < C::FM; ++i) {
-        const int row = min(m0 + wm * C::WTM + i * 16 + r16, M - 1);
-        const float a = ep.ext_stats[2 * row], q = ep.ext_stats[2 * row + 1];
+        float a, q;
+        if (C::EPI_BATCH && act != ACT_SWIGLU) {  // requested after the main loop by K group 0 (the others' are unused)
+          a = q = 0.f;
+          if (kgrp == 0) {
+            consume_from_here(pre_st[i]);
+            a = __uint_as_float(pre_st[i][0]);
+            q = __uint_as_float(pre_st[i][1]);
+          }
+        } else {
+          const int row = min(m0 + wm * C::WTM + i * 16 + r16, M - 1);
+          a = ep.ext_stats[2 * row];
+          q = ep.ext_stats[2 * row + 1];
+        }
         const float mu = ln_mode == 1 ? a * inv_k : 0.f;
         ln_mu[i] = mu;
         ln_rs[i] = rsqrtf(fmaxf(q * inv_k - mu * mu, 0.f) + ln_eps);
@@ -801,14 +960,12 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
   // ~1.2 TB/s on the 51 MB LM-head output; full rows run at the HBM write rate.
   // BNC 16-B chunks per tile row, stored in rows of BNP (power of two >= 8) chunks: image chunk
   // c of row r sits at c ^ (r & 7), and BNP consecutive lanes own one row in the store pass
-  constexpr int BNC = C::BN / 8;
-  constexpr int BNP = BNC <= 8 ? 8 : BNC <= 16 ? 16 : BNC <= 32 ? 32 : 64;
   static_assert(C::BN % 8 == 0 && BNC <= 64, "staged epilogue: BN % 8 == 0, BN <= 512");
   static_assert(C::BM * BNP * 16 <= C::LDS_UNITS * 16, "output tile image must fit the staging LDS");
   static_assert((C::BM * BNP) % 64 == 0 && ((C::BM * BNP) % C::T == 0 || C::BM * BNP < C::T),
                 "store pass: every wave makes the same number of passes (shuffles stay wave-uniform)");
   bf16* img = reinterpret_cast<bf16*>(smem);
-  __syncthreads();  // every wave is done with the staging buffers (and the norm statistics)
+  epi_barrier<C::EPI_BATCH>();  // every wave is done with the staging buffers (and the norm statistics)
   // The activation / folded-norm / RoPE choice is made ONCE per tile and the fragment pass is
   // instantiated per combination: a runtime switch per output value (apply_act) unrolled over
   // the 128 values per lane of a 256 x 256 tile compiled to ~25k instructions of branches
@@ -826,6 +983,36 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
       const bool full = col + 3 < N;
       float bv[4] = {0.f, 0.f, 0.f, 0.f};
       float csv[4] = {0.f, 0.f, 0.f, 0.f};  // colsum(W') of the 4 columns (folded norm)
+      if constexpr (C::EPI_BATCH) {
+        // requested after the main loop from clamped addresses: a column past N reads as 0
+        if (bias) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bv[e] = 0.f;
+          uint32_t w[4];  // (a bf16 is the high half of its fp32)
+          if (pre_bvec) {
+            consume_from_here(pre_bv[j]);
+            const uint32_t p0 = pre_bv[j][0], p1 = pre_bv[j][1];
+            w[0] = p0 << 16;
+            w[1] = p0 & 0xffff0000u;
+            w[2] = p1 << 16;
+            w[3] = p1 & 0xffff0000u;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              consume_from_here(pre_bs[j][e]);
+              w[e] = pre_bs[j][e] << 16;
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bv[e] = col + e < N ? __uint_as_float(w[e]) : 0.f;
+        }
+        if constexpr (LNM) {
+          consume_from_here(pre_cs[j]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) csv[e] = col + e < N ? __uint_as_float(pre_cs[j][e]) : 0.f;
+        }
+        (void)full;
+      } else {
       if (bias) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) bv[e] = col + e < N ? bf2f(bias[col + e]) : 0.f;
@@ -839,6 +1026,7 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
 #pragma unroll
           for (int e = 0; e < 4; ++e) csv[e] = col + e < N ? ln_colsum[col + e] : 0.f;
         }
+      }
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i) {
@@ -876,10 +1064,17 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
       default: by_ln(std::integral_constant<int, ACT_NONE>{}, B0{}); break;
     }
   }
-  __syncthreads();
+  epi_barrier<C::EPI_BATCH>();  // the image is complete (the residual requests stay in flight)
   DLS_STAMP(2)
   const bool v16 = ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2)) & 15) == 0 &&
                    (!R || ((reinterpret_cast<uintptr_t>(R) | ((uintptr_t)ldr * 2)) & 15) == 0);
+  if constexpr (C::EPI_BATCH) {
+    if (pre_res) {
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p)
+        if (tid + p * C::T < C::BM * BNP) consume_from_here(pre_r[p]);
+    }
+  }
   const bf16x8* img8 = reinterpret_cast<const bf16x8*>(img);
   const int tid_ = threadIdx.x;
   // consecutive groups of BNP threads own one tile row per pass (lanes past BNC idle)
@@ -892,7 +1087,17 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
     if (cc < BNC && row < M && col < N) {
       if (v16 && col + 8 <= N) {
         if (R) {
-          const bf16x8 r8 = *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+          bf16x8 r8;
+          if constexpr (C::EPI_BATCH) {
+            // the segment as requested after the main loop (pass q / T of this thread)
+            u32x4 rp = pre_r[0];
+#pragma unroll
+            for (int p = 1; p < NPASS; ++p) rp = q / C::T == p ? pre_r[p] : rp;
+            r8 = pre_res ? *reinterpret_cast<const bf16x8*>(&rp)
+                         : *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+          } else {
+            r8 = *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+          }
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(o[e]) + bf2f(r8[e]));
         }
