@@ -752,8 +752,10 @@ def rope_(qkv, S, n_head, n_kv_head, head_dim, k_col, cos_t, sin_t):
 def moe_router(logits, topk):
     if _gpu(logits):
         return tuple(ext().moe_router(logits.contiguous(), int(topk)))
-    lf = logits.float()
-    val, idx = torch.topk(lf, topk, dim=-1)
+    # the kernel's rule (moe.hip select_topk): descending logit, ties to the lower expert index —
+    # a stable sort; torch.topk breaks ties arbitrarily
+    val, idx = torch.sort(logits.float(), dim=-1, descending=True, stable=True)
+    val, idx = val[..., :topk], idx[..., :topk]
     w = torch.softmax(val, dim=-1)
     return idx.to(torch.int32), w
 

@@ -5,11 +5,16 @@ asymmetric-B identity test that catches a transposed C write
 (cdna_hip_programming.md §3 "Always A=I-check with ASYMMETRIC B").
 """
 import math
+import os
+import sys
 
 import pytest
 import torch
 
 from distributed_llm_scheduler_amd import ops
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from moe_checks import GATE_TOL as MOE_GATE_TOL  # noqa: E402  (measured in test_moe_kernels_gpu.py)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -175,13 +180,16 @@ def test_rope(D):
 
 def test_moe_pipeline():
     M, E, k, H, F = 300, 8, 2, 128, 96
-    # tie-free logits (bf16 random values collide; top-k order among ties is unspecified)
+    # tie-free logits (bf16 random values collide; ties — lower expert index first — are
+    # test_moe_kernels_gpu.py's subject)
     g = torch.Generator().manual_seed(21)
     logits = torch.stack([torch.randperm(E, generator=g) for _ in range(M)]).float().mul(0.25)
     logits = logits.to(torch.bfloat16).to(DEV)
     idx, w = ops.moe_router(logits, k)
     ridx, rw = ops.moe_router(logits.cpu(), k)
     assert torch.equal(idx.cpu().sort(-1).values, ridx.sort(-1).values)
+    gate_err = (w.cpu().double() - rw.double()).abs().max().item()
+    assert torch.equal(idx.cpu(), ridx) and gate_err <= MOE_GATE_TOL, f"gates differ from the CPU path by {gate_err:.3g}"
     src, slot, off = ops.moe_align(idx, E)
     rsrc, rslot, roff = ops.moe_align(idx.cpu(), E)
     assert torch.equal(off.cpu(), roff) and torch.equal(src.cpu(), rsrc) and torch.equal(slot.cpu(), rslot)
