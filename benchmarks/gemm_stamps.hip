@@ -1,7 +1,9 @@
 // In-kernel phase timing of one LDS-DMA GEMM config (diagnostic executable): compiles
 // csrc/kernels/gemm_glds_impl.h (configs 34, 13, 24, 27, 17, 45, 25, 22) into this translation unit
 // with DLS_STAMP recording s_memrealtime (100 MHz) per workgroup at: tile start, after the main
-// loop, after the K-group sum, after the output image is in LDS, after the store pass.
+// loop (1), after the K groups' fragments are summed or, on the one-pass configs (Cfg::ONE_PASS),
+// handed over through LDS (7), after the output image is in LDS (2; the one-pass finish has no
+// image and never stamps it), after the stores (3).
 //
 // The epilogue mode attaches the operands a model step attaches (none: a bare GEMM):
 //   res     bias + residual + stats_out            (GPT-2 out-proj, fc2)
@@ -125,15 +127,18 @@ int main(int argc, char** argv) {
     t0 = std::min(t0, s[0]);
     tend = std::max(tend, s[3]);
   }
-  // phases: 0 -> 1 main loop, 1 -> 7 K-group sum, 7 -> 2 image, 2 -> 3 store
+  // phases: 0 -> 1 main loop, 1 -> 7 K groups through LDS (staged: group 0 holds their sum;
+  // one-pass: every group's fragments are in LDS), 7 -> 2 image (staged only), 2 -> 3 finish and
+  // store (staged: the store pass; one-pass: sum, epilogue and store — from stamp 7)
   std::vector<double> d_main, d_sum, d_img, d_store, d_epi, start, end;
   for (int b = 0; b < kMaxBlocks; ++b) {
     const unsigned long long* s = &st[b * kSlots];
     if (!s[0]) continue;
     d_main.push_back((s[1] - s[0]) * 0.01);
     d_sum.push_back((s[7] - s[1]) * 0.01);
-    d_img.push_back((s[2] - s[7]) * 0.01);
-    d_store.push_back((s[3] - s[2]) * 0.01);
+    const unsigned long long s2 = s[2] ? s[2] : s[7];  // (one-pass: no image phase)
+    d_img.push_back((s2 - s[7]) * 0.01);
+    d_store.push_back((s[3] - s2) * 0.01);
     d_epi.push_back((s[3] - s[1]) * 0.01);
     start.push_back((s[0] - t0) * 0.01);
     end.push_back((s[3] - t0) * 0.01);
@@ -151,9 +156,9 @@ int main(int argc, char** argv) {
          N, K, mode, ms * 1e3, d_main.size(), (tend - t0) * 0.01);
   printf("  start offset   min %.2f med %.2f max %.2f us\n", q(start, 0), q(start, .5), q(start, 1));
   printf("  main loop      min %.2f med %.2f max %.2f mean %.2f us\n", q(d_main, 0), q(d_main, .5), q(d_main, 1), mean(d_main));
-  printf("  K-group sum    min %.2f med %.2f max %.2f mean %.2f us\n", q(d_sum, 0), q(d_sum, .5), q(d_sum, 1), mean(d_sum));
+  printf("  K groups > LDS min %.2f med %.2f max %.2f mean %.2f us\n", q(d_sum, 0), q(d_sum, .5), q(d_sum, 1), mean(d_sum));
   printf("  image to LDS   min %.2f med %.2f max %.2f mean %.2f us\n", q(d_img, 0), q(d_img, .5), q(d_img, 1), mean(d_img));
-  printf("  store pass     min %.2f med %.2f max %.2f mean %.2f us\n", q(d_store, 0), q(d_store, .5), q(d_store, 1), mean(d_store));
+  printf("  finish + store min %.2f med %.2f max %.2f mean %.2f us\n", q(d_store, 0), q(d_store, .5), q(d_store, 1), mean(d_store));
   printf("  after the loop min %.2f med %.2f max %.2f mean %.2f us\n", q(d_epi, 0), q(d_epi, .5), q(d_epi, 1), mean(d_epi));
   printf("  end offset     min %.2f med %.2f max %.2f us\n", q(end, 0), q(end, .5), q(end, 1));
   return 0;

@@ -28,8 +28,9 @@
 
 // In-kernel phase stamps for diagnostic builds (benchmarks/gemm_stamps.hip defines it before
 // including this file); empty in the library. glds_tile stamps 0 tile start, 1 after the main
-// loop, 7 after the K-group sum, 2 after the output image is in LDS, 3 after the store pass
-// (4-6 belong to gemm_fused.hip).
+// loop, 7 after the K-group sum (one-pass finish: after every K group's fragments are in LDS),
+// 2 after the output image is in LDS (never on the one-pass finish: it has no image), 3 after
+// the stores (4-6 belong to gemm_fused.hip).
 #ifndef DLS_STAMP
 #define DLS_STAMP(k)
 #endif
@@ -79,7 +80,9 @@ __device__ __forceinline__ void epi_barrier() {
 // KG_ = K groups: KG wave groups of WM x WN waves share each output tile; a stage holds KG
 // consecutive 64-deep K-tiles and group g multiplies tile g of every stage (intra-block
 // split-K: KG x the waves — and DMA issuers — per CU on a skinny grid, no reduce kernel; the
-// groups' accumulators are summed through LDS before the epilogue).
+// groups' accumulators meet in LDS after the K loop: the small wave tiles sum and finish them
+// there in one pass by every thread (ONE_PASS below), the others sum them into group 0, which
+// runs the staged epilogue).
 // RING_ = 1: the 256x256 half-tile ring main loop (mainloop_ring) instead of whole-K-tile stages
 // OCC_: waves per SIMD the kernel must allow (__launch_bounds__' second argument): 2 for the
 // 4-wave tiles meant to run two workgroups per CU (at most 256 VGPRs + AGPRs per wave)
@@ -113,7 +116,8 @@ struct Cfg {
   static_assert(STAGES >= 2 && STAGES <= 8, "stages");
   static_assert(LDS_UNITS * 16 <= 163840, "LDS budget");
   static_assert(KG == 1 || (BXS == 0 && PRIO == 0), "K groups use the joint ring");
-  // one LDS region of NW * FM * FN KiB per K group past the first (all written before ONE barrier)
+  // K-group sum into group 0 (split-K slices, SwiGLU, tiles without ONE_PASS): one LDS region of
+  // NW * FM * FN KiB per K group past the first (all written before ONE barrier)
   static_assert(KG == 1 || (KG - 1) * NW * 64 * FM * FN * 16 <= LDS_UNITS * 16, "K-group reduction must fit the LDS");
   // Batched epilogue operand requests (glds_tile): the small wave tiles of the skinny M = 512
   // GEMMs, whose body is a few us and whose epilogue operands (row statistics, bias, colsum,
@@ -122,6 +126,14 @@ struct Cfg {
   // The large tiles (128 accumulator registers and more next to their fragment registers) keep
   // the in-place loads — their epilogue is a small share of a long body.
   static constexpr bool EPI_BATCH = FM * FN <= 4;
+  // One-pass finish of a K-grouped tile (glds_tile): EVERY K group writes its fp32 fragments to
+  // an LDS region of its own, one barrier, and every thread of the block sums, finishes and
+  // stores one 16-byte row segment — instead of K group 0 summing the others' fragments,
+  // writing a bf16 tile image to LDS and the block reading that back (two trips through LDS, the
+  // finishing arithmetic on 1 / KG of the waves). Configs 16, 17, 20, 27 and 45; a config that
+  // loses with it is gated out here.
+  static constexpr bool ONE_PASS = KG > 1 && EPI_BATCH;
+  static_assert(!ONE_PASS || KG * NW * 64 * FM * FN * 16 <= LDS_UNITS * 16, "one region per K group must fit the LDS");
   static_assert(!RING || (BM == 256 && BN == 256 && WM == 2 && WN == 4 && STAGES == 2 && KG == 1 && BXS == 0),
                 "the ring main loop is written for 256x256 tiles, 8 waves as 2 x 4, 8 x 16 KiB slots");
 };
@@ -570,8 +582,14 @@ __device__ __forceinline__ void mainloop_split(bf16x8* smem, const bf16* __restr
 // APOL: the A rows' DMA cache policy (joint rings; mainloop_joint); PUB: the output tile is
 // stored write-through (sc1) so workgroups of the SAME launch on other XCDs can read it after
 // an agent-scope arrival count (gemm_fused.hip) — both 0 / false in every ordinary launch
+// ONEP: the one-pass finish where the config has it (Cfg::ONE_PASS): 1 yes; 2 yes, from a kernel
+// that walks several tiles (the thread <-> segment mapping is then derived again per tile: hoisted
+// out of the walk its offsets stay in registers across the main loop — the row-ranged config 17
+// lost a wave of occupancy, the walks of config 20 spilled 20-60 VGPRs); 0 no — the persistent
+// walk of the 16-wave config 20 alone, whose kernel (128 VGPRs at most) spilled 22 VGPRs with it
+// against 4 without
 template <class C, int LN, int WPOL = 0, bool SKIP = false, bool GATHER = false, int APOL = 0, bool PUB = false,
-          int SPOL = 0>
+          int SPOL = 0, int ONEP = 1>
 __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__ A, int lda,
                                           const bf16* __restrict__ W, int ldw, bf16* __restrict__ Cp, int ldc,
                                           const bf16* __restrict__ bias, const bf16* __restrict__ R, int ldr,
@@ -696,6 +714,258 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
       }
     }
   };
+  // The activation / folded-norm / RoPE choice is made ONCE per tile and the finishing pass is
+  // instantiated per combination: a runtime switch per output value (apply_act) unrolled over
+  // the 128 values per lane of a 256 x 256 tile compiled to ~25k instructions of branches
+  // around inlined GeLU / SiLU bodies, and the instruction fetches of jumping through them made
+  // this pass take 19.5 us per tile on MI355X (benchmarks/gemm_stamps.hip) — 3x the main loop
+  // of the GPT-2 LM head.
+  using B0 = std::integral_constant<bool, false>;
+  using B1 = std::integral_constant<bool, true>;
+  auto per_epilogue = [&](auto&& pass) {  // pass(act_tag, ln_tag, rope_tag)
+    auto by_ln = [&](auto act_tag, auto rope_tag) {
+      if (ln_mode != 0) pass(act_tag, B1{}, rope_tag);
+      else pass(act_tag, B0{}, rope_tag);
+    };
+    if (rope.cols) {
+      by_ln(std::integral_constant<int, ACT_NONE>{}, B1{});  // RoPE epilogues carry no activation
+    } else {
+      switch (act) {
+        case ACT_GELU_TANH: by_ln(std::integral_constant<int, ACT_GELU_TANH>{}, B0{}); break;
+        case ACT_SILU: by_ln(std::integral_constant<int, ACT_SILU>{}, B0{}); break;
+        case ACT_RELU: by_ln(std::integral_constant<int, ACT_RELU>{}, B0{}); break;
+        default: by_ln(std::integral_constant<int, ACT_NONE>{}, B0{}); break;
+      }
+    }
+  };
+  // One finished 16-byte row segment (8 bf16 of tile row rl, 16-B chunk cc) on its way out: the
+  // residual add, the store, and the row statistics of what was stored. rp: the residual
+  // segment as requested after the main loop (read only under pre_res). Every lane of a wave
+  // calls it (the statistics' shuffles span the BNP lanes of a row).
+  const bool v16 = ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2)) & 15) == 0 &&
+                   (!R || ((reinterpret_cast<uintptr_t>(R) | ((uintptr_t)ldr * 2)) & 15) == 0);
+  auto store_segment = [&](bf16x8 o, int rl, int cc, const u32x4& rp) {
+    const int row = m0 + rl, col = n0 + cc * 8;
+    float s1 = 0.f, s2 = 0.f;
+    if (cc < BNC && row < M && col < N) {
+      if (v16 && col + 8 <= N) {
+        if (R) {
+          bf16x8 r8;
+          if constexpr (C::EPI_BATCH) {
+            r8 = pre_res ? *reinterpret_cast<const bf16x8*>(&rp)
+                         : *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+          } else {
+            r8 = *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(o[e]) + bf2f(r8[e]));
+        }
+        if constexpr (PUB || SPOL != 0) {  // PUB: write-through, the row segment leaves the XCD's
+          // L2 for memory; SPOL: the store's cache policy (nt: streaming output)
+          const auto rs = __builtin_amdgcn_make_buffer_rsrc(Cp, 0, 0x7fffffff, 0x00020000);
+          __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&o), rs,
+                                                 (int)(((size_t)row * ldc + col) * 2), 0, PUB ? 16 : SPOL);
+        } else {
+          *reinterpret_cast<bf16x8*>(Cp + (size_t)row * ldc + col) = o;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float y = bf2f(o[e]);
+          s1 += y;
+          s2 += y * y;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          if (col + e >= N) continue;
+          float x = bf2f(o[e]);
+          if (R) x += bf2f(R[(size_t)row * ldr + col + e]);
+          const bf16 ob = f2bf(x);
+          Cp[(size_t)row * ldc + col + e] = ob;
+          const float y = bf2f(ob);
+          s1 += y;
+          s2 += y * y;
+        }
+      }
+    }
+    if (ep.stats_out) {
+#pragma unroll
+      for (int o_ = 1; o_ < BNP; o_ <<= 1) {
+        s1 += __shfl_xor(s1, o_, 64);
+        s2 += __shfl_xor(s2, o_, 64);
+      }
+      if (cc == 0 && row < M) {
+        atomicAdd(ep.stats_out + 2 * row, s1);
+        atomicAdd(ep.stats_out + 2 * row + 1, s2);
+      }
+    }
+  };
+  if constexpr (C::ONE_PASS && ONEP != 0) {
+    // One-pass finish (Cfg::ONE_PASS). A split-K slice (partial store or in-launch combine) and
+    // SwiGLU return before the staged epilogue and keep the K-group sum below.
+    static_assert(!LN, "K-grouped tiles take no in-kernel row statistics (launch_gemm_glds)");
+    static_assert(BNP == 8 && C::BM * BNP <= C::T && (C::BM * BNP) % 64 == 0,
+                  "one 16-B segment per thread, 8 lanes per tile row, whole waves");
+    if (part == nullptr && act != ACT_SWIGLU) {
+      // Thread tid < BM * 8 owns chunk cc = tid % 8 (columns 8cc .. 8cc+7) of tile row
+      // rl = tid / 8 — the store pass's mapping; the waves past BM * 8 (config 45: 5 of 8, config
+      // 20: 8 of 16) only hand their fragments over. All operands of the segment are requested
+      // here, in one batch, as request_operands does for the staged epilogue: range-checked
+      // buffer loads (rows past M and, with the vector forms, columns past N read zeros), no
+      // barrier between here and their use waits on vmcnt.
+      int tid1 = tid;
+      if constexpr (ONEP == 2) asm volatile("" : "+v"(tid1));  // (tile walks: derived HERE, per tile)
+      const int lane1 = tid1 & 63, kgrp1 = (tid1 >> 6) / C::NW, wq1 = (tid1 >> 6) % C::NW, wn1 = wq1 % C::WN;
+      const bool own = tid1 < C::BM * BNP;  // (wave-uniform)
+      const int rl = tid1 / BNP, cc = tid1 % BNP;
+      const int row = m0 + rl, col = n0 + cc * 8;
+      u32x2 o_st;        // fp32 bits of the row's (sum, sum of squares)
+      u32x2 o_bv[2];     // pre_bvec: 4 bf16 each
+      uint32_t o_bs[8];  // else: one bf16 (low half) per register
+      u32x4 o_cs[2];     // fp32 bits
+      u32x4 o_r;
+      if (own) {
+        constexpr int kRaw = 0x00020000;  // raw buffer, 32-bit data
+        if (ln_mode != 0) {
+          const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ep.ext_stats), 0, M * 8, kRaw);
+          o_st = __builtin_amdgcn_raw_buffer_load_b64(rs, row * 8, 0, 0);
+        }
+        if (bias) {
+          if (pre_bvec) {
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(bias), 0, N * 2, kRaw);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) o_bv[h] = __builtin_amdgcn_raw_buffer_load_b64(rs, col * 2 + h * 8, 0, 0);
+          } else {
+            const unsigned short* b16 = reinterpret_cast<const unsigned short*>(bias);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o_bs[e] = b16[min(col + e, N - 1)];
+          }
+        }
+        if (ln_mode != 0) {
+          if (pre_cvec) {
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ln_colsum), 0, N * 4, kRaw);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) o_cs[h] = __builtin_amdgcn_raw_buffer_load_b128(rs, col * 4 + h * 16, 0, 0);
+          } else {
+            const uint32_t* c32 = reinterpret_cast<const uint32_t*>(ln_colsum);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o_cs[e >> 2][e & 3] = c32[min(col + e, N - 1)];
+          }
+        }
+        if (pre_res) {
+          // (the descriptor ends with row M-1's N-th column, as in request_operands)
+          const auto rs =
+              __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(R), 0, (int)(((size_t)(M - 1) * ldr + N) * 2), kRaw);
+          o_r = __builtin_amdgcn_raw_buffer_load_b128(rs, (row * ldr + col) * 2, 0, 0);
+        }
+      }
+      // Fragment regions: K group g owns REG f32x4 records at red + g * REG; the record of
+      // fragment (i, j) of wave wq = wm * WN + wn and lane (g4i = lane >> 4, r16 = lane & 15) —
+      // row wm * WTM + 16 i + r16, columns cl .. cl + 3, cl = wn * WTN + 16 j + 4 g4i — sits at
+      //   ((i * FN + j) * NW + wq) * 64 + 16 * g4i + (r16 ^ (((cl >> 3) & 3) << 2)).
+      // Write side: 8 consecutive lanes share g4i, so the XOR permutes them inside their own 8
+      // records (128 B): every ds_write_b128 group covers the 32 write banks once. Read side: the
+      // 16 lanes of a ds_read_b128 group are 4 consecutive chunks cc of each of 4 tile rows whose
+      // r16 differ in bits 0-1 only; record index mod 16 (the 16-B slot of the 256-B bank row)
+      // is r16 ^ ((cc & 3) << 2) — 16 different slots, conflict-free (unswizzled: 4-way). The two
+      // records of a segment (columns 8cc .. +3 and +4 .. +7: g4i and g4i + 1) are 16 apart.
+      constexpr int REG = C::NW * C::FM * C::FN * 64;
+      f32x4* red = reinterpret_cast<f32x4*>(smem);
+      epi_barrier<true>();  // every wave is done with the staging buffers
+#pragma unroll
+      for (int i = 0; i < C::FM; ++i)
+#pragma unroll
+        for (int j = 0; j < C::FN; ++j) {
+          const int cl = wn1 * C::WTN + j * 16 + (lane1 >> 4) * 4;
+          red[kgrp1 * REG + ((i * C::FN + j) * C::NW + wq1) * 64 + (lane1 & 48) +
+              ((lane1 & 15) ^ (((cl >> 3) & 3) << 2))] = acc[i][j];
+        }
+      epi_barrier<true>();  // every group's fragments are in LDS (the operand requests stay in flight)
+      DLS_STAMP(7)
+      if (own) {
+        // (chunks past the tile's BNC — 48-column tiles — read chunk BNC - 1 again and store nothing)
+        const int ccr = min(cc, BNC - 1), cl0 = ccr * 8;
+        const int rec = (((rl % C::WTM) / 16 * C::FN + (cl0 % C::WTN) / 16) * C::NW + (rl / C::WTM) * C::WN +
+                         cl0 / C::WTN) * 64 + (cl0 & 8) * 4 + ((rl & 15) ^ ((ccr & 3) << 2));
+        f32x4 part_lo[C::KG], part_hi[C::KG];
+#pragma unroll
+        for (int g2 = 0; g2 < C::KG; ++g2) {
+          part_lo[g2] = red[g2 * REG + rec];
+          part_hi[g2] = red[g2 * REG + rec + 16];
+        }
+        // the K groups' sum in the order ((g0 + g1) + g2) + g3, as group 0 added them
+        f32x4 lo = part_lo[0], hi = part_hi[0];
+#pragma unroll
+        for (int g2 = 1; g2 < C::KG; ++g2) {
+          lo += part_lo[g2];
+          hi += part_hi[g2];
+        }
+        float ln_rs1 = 0.f, ln_mu1 = 0.f;
+        if (ln_mode != 0) {
+          const float inv_k = 1.0f / (float)K;
+          consume_from_here(o_st);
+          const float a = __uint_as_float(o_st[0]), q = __uint_as_float(o_st[1]);
+          const float mu = ln_mode == 1 ? a * inv_k : 0.f;
+          ln_mu1 = mu;
+          ln_rs1 = rsqrtf(fmaxf(q * inv_k - mu * mu, 0.f) + ln_eps);
+        }
+        bf16x8 o;
+        auto finish = [&](auto act_tag, auto ln_tag, auto rope_tag) {
+          constexpr int ACT = decltype(act_tag)::value;
+          constexpr bool LNM = decltype(ln_tag)::value, ROPE = decltype(rope_tag)::value;
+          float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          float csv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // colsum(W') of the 8 columns (folded norm)
+          if (bias) {
+            uint32_t w[8];  // (a bf16 is the high half of its fp32)
+            if (pre_bvec) {
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                consume_from_here(o_bv[h]);
+                const uint32_t p0 = o_bv[h][0], p1 = o_bv[h][1];
+                w[4 * h + 0] = p0 << 16;
+                w[4 * h + 1] = p0 & 0xffff0000u;
+                w[4 * h + 2] = p1 << 16;
+                w[4 * h + 3] = p1 & 0xffff0000u;
+              }
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) {
+                consume_from_here(o_bs[e]);
+                w[e] = o_bs[e] << 16;
+              }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) bv[e] = col + e < N ? __uint_as_float(w[e]) : 0.f;
+          }
+          if constexpr (LNM) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) consume_from_here(o_cs[h]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) csv[e] = col + e < N ? __uint_as_float(o_cs[e >> 2][e & 3]) : 0.f;
+          }
+          float v[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float x = e < 4 ? lo[e & 3] : hi[e & 3];
+            // W.LN(x) = rstd * (W' x - mu * colsum(W')) + (bias + W b), W' = W * ln_w (host-derived)
+            if constexpr (LNM) v[e] = act_c<ACT>(ln_rs1 * (x - ln_mu1 * csv[e]) + bv[e]);
+            else v[e] = act_c<ACT>(alpha * x + bv[e]);
+          }
+          if constexpr (ROPE) {
+            rope_pairs<4>(v, row, col, rope);
+            rope_pairs<4>(v + 4, row, col + 4, rope);
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = f2bf(v[e]);
+        };
+        per_epilogue(finish);
+        if (pre_res) consume_from_here(o_r);
+        store_segment(o, rl, cc, o_r);
+      }
+      DLS_STAMP(3)
+      return;
+    }
+  }
   if constexpr (C::EPI_BATCH) {
     // (a split-K slice stores a partial tile, and SwiGLU has its own epilogue: neither reaches
     // the staged epilogue; the in-launch combine asks once it knows it is the last arriver)
@@ -966,12 +1236,7 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
                 "store pass: every wave makes the same number of passes (shuffles stay wave-uniform)");
   bf16* img = reinterpret_cast<bf16*>(smem);
   epi_barrier<C::EPI_BATCH>();  // every wave is done with the staging buffers (and the norm statistics)
-  // The activation / folded-norm / RoPE choice is made ONCE per tile and the fragment pass is
-  // instantiated per combination: a runtime switch per output value (apply_act) unrolled over
-  // the 128 values per lane of a 256 x 256 tile compiled to ~25k instructions of branches
-  // around inlined GeLU / SiLU bodies, and the instruction fetches of jumping through them made
-  // this pass take 19.5 us per tile on MI355X (benchmarks/gemm_stamps.hip) — 3x the main loop
-  // of the GPT-2 LM head.
+  // (one instance of the fragment pass per activation / folded-norm / RoPE choice: per_epilogue)
   auto image_pass = [&](auto act_tag, auto ln_tag, auto rope_tag) {
     constexpr int ACT = decltype(act_tag)::value;
     constexpr bool LNM = decltype(ln_tag)::value, ROPE = decltype(rope_tag)::value;
@@ -1048,26 +1313,9 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
       }
     }
   };
-  using B0 = std::integral_constant<bool, false>;
-  using B1 = std::integral_constant<bool, true>;
-  auto by_ln = [&](auto act_tag, auto rope_tag) {
-    if (ln_mode != 0) image_pass(act_tag, B1{}, rope_tag);
-    else image_pass(act_tag, B0{}, rope_tag);
-  };
-  if (rope.cols) {
-    by_ln(std::integral_constant<int, ACT_NONE>{}, B1{});  // RoPE epilogues carry no activation
-  } else {
-    switch (act) {
-      case ACT_GELU_TANH: by_ln(std::integral_constant<int, ACT_GELU_TANH>{}, B0{}); break;
-      case ACT_SILU: by_ln(std::integral_constant<int, ACT_SILU>{}, B0{}); break;
-      case ACT_RELU: by_ln(std::integral_constant<int, ACT_RELU>{}, B0{}); break;
-      default: by_ln(std::integral_constant<int, ACT_NONE>{}, B0{}); break;
-    }
-  }
+  per_epilogue(image_pass);
   epi_barrier<C::EPI_BATCH>();  // the image is complete (the residual requests stay in flight)
   DLS_STAMP(2)
-  const bool v16 = ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2)) & 15) == 0 &&
-                   (!R || ((reinterpret_cast<uintptr_t>(R) | ((uintptr_t)ldr * 2)) & 15) == 0);
   if constexpr (C::EPI_BATCH) {
     if (pre_res) {
 #pragma unroll
@@ -1081,65 +1329,14 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
 #pragma unroll 2
   for (int q = tid_; q < C::BM * BNP; q += C::T) {
     const int rl = q / BNP, cc = q % BNP;
-    const int row = m0 + rl, col = n0 + cc * 8;
-    bf16x8 o = img8[rl * BNP + (cc ^ (rl & 7))];
-    float s1 = 0.f, s2 = 0.f;
-    if (cc < BNC && row < M && col < N) {
-      if (v16 && col + 8 <= N) {
-        if (R) {
-          bf16x8 r8;
-          if constexpr (C::EPI_BATCH) {
-            // the segment as requested after the main loop (pass q / T of this thread)
-            u32x4 rp = pre_r[0];
+    // the residual segment as requested after the main loop (pass q / T of this thread)
+    u32x4 rp;
+    if constexpr (C::EPI_BATCH) {
+      rp = pre_r[0];
 #pragma unroll
-            for (int p = 1; p < NPASS; ++p) rp = q / C::T == p ? pre_r[p] : rp;
-            r8 = pre_res ? *reinterpret_cast<const bf16x8*>(&rp)
-                         : *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
-          } else {
-            r8 = *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(o[e]) + bf2f(r8[e]));
-        }
-        if constexpr (PUB || SPOL != 0) {  // PUB: write-through, the row segment leaves the XCD's
-          // L2 for memory; SPOL: the store's cache policy (nt: streaming output)
-          const auto rs = __builtin_amdgcn_make_buffer_rsrc(Cp, 0, 0x7fffffff, 0x00020000);
-          __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&o), rs,
-                                                 (int)(((size_t)row * ldc + col) * 2), 0, PUB ? 16 : SPOL);
-        } else {
-          *reinterpret_cast<bf16x8*>(Cp + (size_t)row * ldc + col) = o;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float y = bf2f(o[e]);
-          s1 += y;
-          s2 += y * y;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if (col + e >= N) continue;
-          float x = bf2f(o[e]);
-          if (R) x += bf2f(R[(size_t)row * ldr + col + e]);
-          const bf16 ob = f2bf(x);
-          Cp[(size_t)row * ldc + col + e] = ob;
-          const float y = bf2f(ob);
-          s1 += y;
-          s2 += y * y;
-        }
-      }
+      for (int p = 1; p < NPASS; ++p) rp = q / C::T == p ? pre_r[p] : rp;
     }
-    if (ep.stats_out) {
-#pragma unroll
-      for (int o_ = 1; o_ < BNP; o_ <<= 1) {
-        s1 += __shfl_xor(s1, o_, 64);
-        s2 += __shfl_xor(s2, o_, 64);
-      }
-      if (cc == 0 && row < M) {
-        atomicAdd(ep.stats_out + 2 * row, s1);
-        atomicAdd(ep.stats_out + 2 * row + 1, s2);
-      }
-    }
+    store_segment(img8[rl * BNP + (cc ^ (rl & 7))], rl, cc, rp);
   }
   DLS_STAMP(3)
 }
@@ -1181,9 +1378,11 @@ __global__ __launch_bounds__(C::T, C::OCC) void gemm_glds_kernel(const bf16* __r
     // instead of holding the CU (one block per CU cannot overlap them across blocks)
     const int total = ntile * splitk;
     for (int L = blockIdx.x, it = 0; L < total; L += gridDim.x, ++it) {
-      if (it) raw_barrier();  // every wave is done reading the previous tile's output image
+      // every wave is done reading the previous tile's output image (one-pass configs: the K
+      // groups' fragment regions) — the next tile's DMA refills the same staging buffers
+      if (it) raw_barrier();
       const int ks = L / ntile, tile = L % ntile;
-      glds_tile<C, LN>(smem, A, lda, W, ldw, Cp, ldc, bias, R, ldr, part, M, M, N, K, act, alpha, ks, kslice,
+      glds_tile<C, LN, 0, false, false, 0, false, 0, (C::T <= 512 ? 2 : 0)>(smem, A, lda, W, ldw, Cp, ldc, bias, R, ldr, part, M, M, N, K, act, alpha, ks, kslice,
                        tile % tiles_m, tile / tiles_m, ln_colsum, (LN || ep.ext_stats) ? ln_mode : 0, ln_eps, ep);
     }
     return;
@@ -1280,11 +1479,13 @@ __global__ __launch_bounds__(C::T, C::OCC) void gemm_glds_kernel(const bf16* __r
   for (int t = t0; t * C::BM < Mr; t += dt) {                                                                      \
     if (t != t0) raw_barrier(); /* every wave is done reading the staging buffers of the previous tile */          \
     if (C::BXS > 0 && (ep.w_stream & 1))                                                                           \
-      glds_tile<C, 0, kPolStream, true, GA>(smem, Ag, lda, Wg, ldw, Cg, ldc, bias, nullptr, 0, nullptr, Mr, M, N, K, \
-                                            act, alpha, 0, K, t, tn, ln_colsum, 0, ln_eps, ep, ag);                \
+      glds_tile<C, 0, kPolStream, true, GA, 0, false, 0, 2>(smem, Ag, lda, Wg, ldw, Cg, ldc, bias, nullptr, 0,     \
+                                                            nullptr, Mr, M, N, K, act, alpha, 0, K, t, tn,        \
+                                                            ln_colsum, 0, ln_eps, ep, ag);                        \
     else                                                                                                           \
-      glds_tile<C, 0, 0, false, GA>(smem, Ag, lda, Wg, ldw, Cg, ldc, bias, nullptr, 0, nullptr, Mr, M, N, K, act,   \
-                                    alpha, 0, K, t, tn, ln_colsum, 0, ln_eps, ep, ag);                             \
+      glds_tile<C, 0, 0, false, GA, 0, false, 0, 2>(smem, Ag, lda, Wg, ldw, Cg, ldc, bias, nullptr, 0, nullptr,    \
+                                                    Mr, M, N, K, act, alpha, 0, K, t, tn, ln_colsum, 0, ln_eps,   \
+                                                    ep, ag);                                                       \
   }
     if (a_rows) {
       DLS_GROUPED_WALK(true)
@@ -1324,8 +1525,8 @@ __global__ __launch_bounds__(C::T, C::OCC) void gemm_glds_kernel(const bf16* __r
   if (part) part += (size_t)r0 * N;
   for (int t = 0; t * C::BM < Mr; ++t) {
     if (t) raw_barrier();  // every wave is done reading the staging buffers of the previous tile
-    glds_tile<C, 0>(smem, A, lda, W, ldw, Cp, ldc, bias, R, ldr, part, Mr, M, N, K, act, alpha, ks, kslice, t, tn,
-                    ln_colsum, 0, ln_eps, ep);
+    glds_tile<C, 0, 0, false, false, 0, false, 0, 2>(smem, A, lda, W, ldw, Cp, ldc, bias, R, ldr, part, Mr, M, N, K, act,
+                                                     alpha, ks, kslice, t, tn, ln_colsum, 0, ln_eps, ep);
   }
 }
 
