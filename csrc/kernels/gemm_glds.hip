@@ -366,6 +366,25 @@ static_assert(sizeof(kLaunch) / sizeof(kLaunch[0]) == kNumCfg, "one launcher per
 
 int gemm_glds_num_configs() { return kNumCfg; }
 int gemm_glds_kstep(int cfg) { return kKStep[(cfg & (kGemmPersist - 1)) < kNumCfg ? (cfg & (kGemmPersist - 1)) : 3]; }
+void gemm_glds_tile(int cfg, int* bm, int* bn) {
+  const Shape t = kShapes[(cfg & (kGemmPersist - 1)) < kNumCfg ? (cfg & (kGemmPersist - 1)) : 3];
+  *bm = t.bm;
+  *bn = t.bn;
+}
+
+// The config a launch really runs: the persistent flag dropped, in-kernel row statistics and
+// the SwiGLU epilogue moved to a config that has them.
+int gemm_glds_resolve(int cfg, int act, bool ln_in) {
+  cfg &= kGemmPersist - 1;
+  if (ln_in) {
+    if (kShapes[cfg < kNumCfg ? cfg : 3].bm * kShapes[cfg < kNumCfg ? cfg : 3].bn > 256 * 128) cfg = 0;
+    if (cfg < kNumCfg && kKStep[cfg] != 64) cfg = 3;  // K groups: no in-kernel row statistics
+  }
+  // the SwiGLU epilogue pairs 16-column gate/up fragments: wave tiles must be multiples of 32
+  // columns (configs 22-27, 38, 39: 48- / 144-column wave tiles; 36: 112)
+  if (act == kActSwiglu && swiglu_bad(cfg)) cfg = kKStep[cfg] == 64 ? 3 : 17;
+  return cfg < kNumCfg ? cfg : 3;
+}
 
 // Heuristic: largest tile whose grid (times a split-K factor that keeps >= 4 K-tiles per
 // block) reaches ~256 blocks; split-K only when the output grid alone is too small.
@@ -398,16 +417,9 @@ bool launch_gemm_glds(const GemmArgs& a, int cfg, int splitk, void* workspace, h
                       int ln_mode, float ln_eps, const int* rows) {
   float* ws = static_cast<float*>(workspace);
   const bool persist = cfg >= kGemmPersist && !rows;
-  cfg &= kGemmPersist - 1;
-  if (ln_mode != 0 && !a.ext_stats) {
-    splitk = 1;  // in-kernel row statistics need the whole K range in one block
-    if (kShapes[cfg < kNumCfg ? cfg : 3].bm * kShapes[cfg < kNumCfg ? cfg : 3].bn > 256 * 128) cfg = 0;
-    if (cfg < kNumCfg && kKStep[cfg] != 64) cfg = 3;  // K groups: no in-kernel row statistics
-  }
-  // the SwiGLU epilogue pairs 16-column gate/up fragments: wave tiles must be multiples of 32
-  // columns (configs 22-27, 38, 39: 48- / 144-column wave tiles; 36: 112)
-  if (a.act == kActSwiglu && swiglu_bad(cfg)) cfg = kKStep[cfg] == 64 ? 3 : 17;
-  return kLaunch[cfg < kNumCfg ? cfg : 3](a, splitk, ws, s, ln_colsum, ln_mode, ln_eps, rows, persist);
+  const bool ln_in = ln_mode != 0 && !a.ext_stats;
+  if (ln_in) splitk = 1;  // in-kernel row statistics need the whole K range in one block
+  return kLaunch[gemm_glds_resolve(cfg, a.act, ln_in)](a, splitk, ws, s, ln_colsum, ln_mode, ln_eps, rows, persist);
 }
 
 void launch_gemm_glds_grouped(const GemmArgs& a, int cfg, int n_groups, const int* offsets,

@@ -44,7 +44,9 @@ struct GemmArgs {
   //            ln_mode 1/2 and ln_colsum: any tile config, split-K allowed).
   float* stats_out = nullptr;
   const float* ext_stats = nullptr;
-  int* tile_sem = nullptr;  // split-K: >= tiles_m*tiles_n zeroed counters -> combine inside the GEMM launch
+  // split-K: >= tiles_m*tiles_n zeroed counters, in tiles of the config the launch resolves to
+  // (gemm_glds_resolve, gemm_glds_tile) -> combine inside the GEMM launch
+  int* tile_sem = nullptr;
   // post-norm of the FINAL output rows for the next (unfolded) norm: norm_out[M][ldn] =
   // norm(C) * norm_w (+ norm_b); norm_mode 1 LayerNorm, 2 RMSNorm. Split-K launches do it in
   // their row-owning reduce (no separate norm launch); launch_gemm_glds reports whether it did.
@@ -83,6 +85,9 @@ void launch_gemm_bf16(const GemmArgs& a, hipStream_t s);  // register-staged, an
 // LDS-DMA multistage GEMM (K % 64 == 0); split-K partials need workspace_bytes of fp32
 int gemm_glds_num_configs();
 int gemm_glds_kstep(int cfg);  // K granularity of a config (64, or 128 for two K groups)
+void gemm_glds_tile(int cfg, int* bm, int* bn);  // output tile of a config (persistent flag ignored)
+// the config launch_gemm_glds runs for (cfg, activation, folded norm with in-kernel statistics)
+int gemm_glds_resolve(int cfg, int act, bool ln_in);
 // cfg | kGemmPersist: the same tile config as a persistent launch (a resident grid walks the
 // tiles; one tile's store drain overlaps the next tile's first loads)
 constexpr int kGemmPersist = 64;

@@ -21,11 +21,12 @@ hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 // out round-robin so kernels in flight on other streams never share a counter; each tile's
 // last arriver resets its counter, so a region is zero again whenever it is reused.
 constexpr int64_t kSemPool = 1 << 20;
+int64_t sem_next[64];  // per device: the pool index the next reservation starts at
 int* split_k_counters(const at::Tensor& like, int64_t n) {
   // heap-held and never freed: a static tensor's destructor would run after the HIP runtime
   // and the caching allocator have been torn down at interpreter exit
   static at::Tensor* pool = new at::Tensor[64];
-  static int64_t next[64];
+  int64_t* next = sem_next;
   const int d = like.get_device();
   TORCH_CHECK(d >= 0 && d < 64 && n <= kSemPool, "split-K counters");
   if (!pool[d].defined()) pool[d] = at::zeros({kSemPool}, like.options().dtype(at::kInt));
@@ -34,6 +35,10 @@ int* split_k_counters(const at::Tensor& like, int64_t n) {
   int* p = pool[d].data_ptr<int>() + next[d];
   next[d] += n;
   return p;
+}
+int64_t split_k_cursor(int64_t device) {
+  TORCH_CHECK(device >= 0 && device < 64, "split-K counters");
+  return sem_next[device];
 }
 const bool kSplitKFixup = [] {
   const char* e = std::getenv("DLS_SPLITK_FIXUP");
@@ -56,7 +61,9 @@ void check_rows(const at::Tensor& t, const char* name) {
 at::Tensor as2d(const at::Tensor& t) { return t.dim() == 2 ? t : t.reshape({-1, t.size(-1)}); }
 
 // splitk: 0 auto (LDS-DMA path), otherwise forced.
-// config: -1 auto, 0..gemm_glds_num_configs()-1 LDS-DMA kernel, >= kRegStage register-staged kernel.
+// config: -1 auto, 0..gemm_glds_num_configs()-1 LDS-DMA kernel (| kGemmPersist: persistent),
+// kRegStage..kRegStage+3 register-staged kernel (ids that would also read as persistent 36..39;
+// persistent launches of configs >= 36 have no id, larger ones are refused).
 // act ACT_SWIGLU: W rows interleave gate/up blocks of 16 (see common.h); the output is N/2 wide.
 // rows (int32[2] on device): only rows [rows[0], rows[1]) of A / out take part (MoE expert ranges).
 constexpr int64_t kRegStage = 100;
@@ -73,6 +80,8 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 double norm_eps, int64_t stream_pol) {
   check_bf16(a_in, "A");
   check_bf16(w, "W");
+  TORCH_CHECK(config < kRegStage + 4, "unknown GEMM config ", config, " (register-staged configs are ", kRegStage,
+              "..", kRegStage + 3, ")");
   at::Tensor a = as2d(a_in);
   check_rows(a, "A");
   check_rows(w, "W");
@@ -126,6 +135,8 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
   if (norm_out.has_value()) {
     TORCH_CHECK(norm_mode == 1 || norm_mode == 2, "norm_mode: 1 LayerNorm, 2 RMSNorm");
     TORCH_CHECK(!swiglu && !rows.has_value() && c.is_contiguous(), "post-norm needs a full, contiguous output");
+    // the norm kernels move rows as 16-byte chunks held in registers (layernorm / rmsnorm check the same)
+    TORCH_CHECK(N % 8 == 0 && N <= 8192, "post-norm needs N % 8 == 0 and N <= 8192, got N = ", N);
     y_n = as2d(*norm_out);
     check_bf16(y_n, "norm_out");
     TORCH_CHECK(y_n.is_contiguous() && y_n.size(0) == M && y_n.size(1) == N, "norm_out must be contiguous [M][N]");
@@ -213,8 +224,13 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
   if (sk > 1) {
     ws = at::empty({(int64_t)gemm_glds_workspace_bytes((int)M, (int)N, sk) / 4}, a.options().dtype(at::kFloat));
     // (a post-norm wants the row-owning reduce kernel, not the in-launch combine)
-    if (kSplitKFixup && !rowp && !norm_out.has_value())
-      g.tile_sem = split_k_counters(a, (M + 63) / 64 * ((N + 63) / 64));
+    if (kSplitKFixup && !rowp && !norm_out.has_value()) {
+      // one counter per output tile of the config the launcher resolves to (sk > 1: no in-kernel
+      // row statistics here)
+      int bm, bn;
+      gemm_glds_tile(gemm_glds_resolve(cfg, (int)act, false), &bm, &bn);
+      g.tile_sem = split_k_counters(a, (M + bm - 1) / bm * ((N + bn - 1) / bn));
+    }
   }
   post_norm(launch_gemm_glds(g, cfg, sk, sk > 1 ? ws.data_ptr() : nullptr, cur_stream(), csp, (int)ln_mode,
                              (float)ln_eps, rowp));
@@ -1305,6 +1321,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_pick_config", &gemm_pick_config);
   m.def("gemm_glds_num_configs", &gemm_glds_num_configs);
   m.def("gemm_glds_kstep", &gemm_glds_kstep);
+  m.def("gemm_glds_tile", [](int64_t cfg) {
+    int bm, bn;
+    gemm_glds_tile((int)cfg, &bm, &bn);
+    return std::make_tuple((int64_t)bm, (int64_t)bn);
+  });
+  m.def("_split_k_cursor", &split_k_cursor);
   m.def("gemm_glds_pick", [](int M, int N, int K) {
     int c, s;
     gemm_glds_pick(M, N, K, &c, &s);
