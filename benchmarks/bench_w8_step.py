@@ -8,11 +8,14 @@ step and kernel launches of the captured step. One JSON line per run.
 
     python benchmarks/bench_w8_step.py --model llama3-8b --modes bf16,fp8,fp8+a8
     python benchmarks/bench_w8_step.py --model llama3-8b --cap 5.993 --modes fp8+a8,mxfp4+a8
+    python benchmarks/bench_w8_step.py --model mixtral-8x7b --modes bf16,fp8-experts,mxfp4-experts+a8
+    python benchmarks/bench_w8_step.py --model mixtral-8x7b --weight-dtype mxfp4-experts [--cap 40]
 
 ``--weight-dtype D`` runs bf16 next to D (``--modes`` lists the modes explicitly). Mode ``fp8+a8``
 is fp8 weights with fp8 activations (``act_dtype="fp8"``: the fp8 x fp8 GEMM); ``--act-dtype fp8``
 adds it to the default modes. Mode ``mxfp4+a8`` is MXFP4 weights with fp8 activations (the W4A8
-GEMM; MXFP4 weights have no other mode).
+GEMM; MXFP4 weights have no other mode), ``mxfp4-experts+a8`` the same for the expert weights of an
+MoE model (the grouped W4A8 GEMM); ``--weight-dtype mxfp4`` / ``mxfp4-experts`` mean these modes.
 """
 from __future__ import annotations
 
@@ -65,13 +68,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--weight-dtype", default="fp8", choices=["fp8", "fp8-experts"],
-                    help="the fp8 mode measured next to bf16 (fp8-experts: the MoE models)")
+    ap.add_argument("--weight-dtype", default="fp8", choices=["fp8", "fp8-experts", "mxfp4", "mxfp4-experts"],
+                    help="the quantised mode measured next to bf16 (fp8-experts, mxfp4-experts: the MoE models; the "
+                         "mxfp4 modes always run with fp8 activations)")
     ap.add_argument("--act-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: also run <--weight-dtype>+a8 (fp8 activations; with --weight-dtype fp8)")
     ap.add_argument("--modes", default=None,
                     help="comma-separated modes: a weight dtype, fp8+a8 or mxfp4+a8 (default: bf16,<--weight-dtype>)")
     a = ap.parse_args()
+    if a.modes is None and a.weight_dtype.startswith("mxfp4"):
+        a.modes = "bf16," + a.weight_dtype + "+a8"
     if a.modes is None:
         a.modes = "bf16," + a.weight_dtype + ("," + a.weight_dtype + "+a8" if a.act_dtype == "fp8" else "")
     for _ in range(a.rounds):

@@ -231,6 +231,38 @@ int gemm_w4a8_max_splitk(int cfg, int K);
 size_t gemm_w4a8_workspace_bytes(int M, int N, int splitk);
 void launch_gemm_w4a8(const GemmW4A8Args& a, hipStream_t s);
 
+// Grouped W4A8 GEMM (gemm_w4a8_grouped.hip): the contract of launch_gemm_w8_grouped with the
+// arithmetic of launch_gemm_w4a8. Group g multiplies the sorted rows [offsets[g], offsets[g+1]) —
+// row r of Aq, or token row a_rows[r] — by its MXFP4 weight: e2m1 pairs [N][K/2] at w_ptrs[g],
+// e8m0 block scales [N][K/32] at s_ptrs[g] (codes 0..254). xscale holds one fp32 scale per SOURCE
+// row of Aq: sorted row r takes xscale[a_rows[r]]. act: ACT_NONE or ACT_SWIGLU (rows of q and s
+// interleaved in blocks of 16, N % 32 == 0). K % 32 == 0, any N, any counts (zero included). No
+// split-K, no atomics, no host sync.
+struct GemmW4A8GroupedArgs {
+  const void* Aq;  // e4m3 [.][lda bytes], rows 16-byte aligned
+  int lda;
+  const float* xscale;  // fp32, one per row of Aq
+  const int* a_rows;    // device int32 [R] or nullptr
+  const int* offsets;   // device int32 [n_groups + 1]
+  const unsigned long long* w_ptrs;  // device [n_groups]
+  const unsigned long long* s_ptrs;  // device [n_groups]
+  const unsigned long long* c_ptrs;  // device [n_groups] or nullptr
+  void* C;                           // bf16 [R][ldc] when c_ptrs == nullptr
+  int ldc;
+  int compact_rows;
+  int R, N, K;  // R: rows all groups cover together (offsets are clamped to it)
+  int act;
+  int n_groups;
+  int config;           // 0..gemm_w4a8_grouped_num_configs()-1
+  int shared_weights;   // as GemmW8GroupedArgs::shared_weights
+  int store_pol;        // as GemmW8Args::store_pol
+  int scales_aligned4;  // every scale tensor's base is 4-byte aligned (with K % 128 == 0: dword loads)
+};
+int gemm_w4a8_grouped_num_configs();
+int gemm_w4a8_grouped_tile_rows(int cfg);  // row-tile height of a config
+int gemm_w4a8_grouped_pick(int rows_hint, int N, int K, int n_groups);
+void launch_gemm_w4a8_grouped(const GemmW4A8GroupedArgs& a, hipStream_t s);
+
 // Per-row e4m3 quantisation (quant_rows.hip): q[m][k] = rne(x[m][k] / scale[m]) with scale[m] the
 // smallest power of two with amax_m / scale[m] <= 448 (all-zero row: 1). x bf16 [M][ldx],
 // q e4m3 [M][ldq], K % 8 == 0.

@@ -1128,6 +1128,100 @@ void gemm_grouped_w8(const at::Tensor& x, const std::vector<at::Tensor>& weights
   launch_gemm_w8_grouped(g, cur_stream());
 }
 
+// gemm_grouped with MXFP4 expert weights and fp8 activation rows (gemm_w4a8_grouped.hip): xq e4m3
+// [rows][K] with one fp32 scale per row (indexed through a_rows when given); weights E x uint8
+// [N][K/2], block scales E x uint8 [N][K/32]; pointer arrays, outputs and config as gemm_grouped_w8.
+void gemm_grouped_w4a8(const at::Tensor& xq, const at::Tensor& xscale, const std::vector<at::Tensor>& weights,
+                       const std::vector<at::Tensor>& scales, const at::Tensor& w_ptrs, const at::Tensor& s_ptrs,
+                       const at::Tensor& offsets, int64_t act, const c10::optional<at::Tensor>& out,
+                       const std::vector<at::Tensor>& outs, const c10::optional<at::Tensor>& out_ptrs, int64_t config,
+                       int64_t rows_hint, const c10::optional<at::Tensor>& a_rows, bool shared_weights,
+                       int64_t store_pol) {
+  const int64_t E = (int64_t)weights.size();
+  TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kFloat8_e4m3fn && xq.dim() == 2,
+              "xq must be a 2-D float8_e4m3fn GPU tensor");
+  TORCH_CHECK(xq.stride(1) == 1 && xq.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "xq must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(E > 0 && (int64_t)scales.size() == E, "one block-scale tensor per expert weight");
+  const int* arp = nullptr;
+  if (a_rows.has_value()) {
+    TORCH_CHECK(a_rows->is_cuda() && a_rows->scalar_type() == at::kInt && a_rows->is_contiguous(),
+                "a_rows: contiguous int32 on the GPU");
+    arp = a_rows->data_ptr<int32_t>();
+  }
+  const int64_t R = a_rows.has_value() ? a_rows->numel() : xq.size(0), K = xq.size(1), N = weights[0].size(0);
+  TORCH_CHECK(xscale.is_cuda() && xscale.device() == xq.device() && xscale.scalar_type() == at::kFloat &&
+                  xscale.is_contiguous() && xscale.numel() == xq.size(0),
+              "xscale must be a contiguous fp32 tensor with one entry per row of xq, on xq's GPU");
+  TORCH_CHECK(act == 0 || act == kActSwiglu, "grouped MXFP4 GEMM: act is none or SwiGLU");
+  const bool sw = act == kActSwiglu;
+  const int64_t NO = sw ? N / 2 : N;
+  TORCH_CHECK(K >= 32 && K % 32 == 0, "the MXFP4 GEMM needs K % 32 == 0, got K = ", K);
+  bool s_al4 = true;
+  for (int64_t e = 0; e < E; ++e) {
+    const auto& w = weights[e];
+    const auto& sc = scales[e];
+    TORCH_CHECK(w.is_cuda() && w.device() == xq.device() && w.scalar_type() == at::kByte,
+                "expert weights must be uint8 tensors (two e2m1 per byte) on xq's GPU");
+    TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == N && w.size(1) == K / 2 &&
+                    reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                "expert weights: contiguous, 16-byte aligned [N][K/2]");
+    TORCH_CHECK(sc.is_cuda() && sc.device() == xq.device() && sc.scalar_type() == at::kByte && sc.is_contiguous() &&
+                    sc.dim() == 2 && sc.size(0) == N && sc.size(1) == K / 32,
+                "expert block scales: contiguous uint8 [N][K/32] on xq's GPU");
+    s_al4 = s_al4 && reinterpret_cast<uintptr_t>(sc.data_ptr()) % 4 == 0;
+  }
+  TORCH_CHECK(w_ptrs.is_cuda() && w_ptrs.scalar_type() == at::kLong && w_ptrs.numel() == E, "w_ptrs int64 [E]");
+  TORCH_CHECK(s_ptrs.is_cuda() && s_ptrs.scalar_type() == at::kLong && s_ptrs.numel() == E, "s_ptrs int64 [E]");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kInt && offsets.numel() == E + 1,
+              "offsets int32 [E+1]");
+  TORCH_CHECK(!sw || N % 32 == 0, "SwiGLU needs interleaved gate/up rows (N % 32 == 0)");
+  int cfg = (int)config;
+  if (cfg < 0)
+    cfg = gemm_w4a8_grouped_pick((int)(rows_hint > 0 ? rows_hint : std::max<int64_t>(1, R / E)), (int)N, (int)K, (int)E);
+  TORCH_CHECK(cfg < gemm_w4a8_grouped_num_configs(), "unknown grouped MXFP4 GEMM config ", cfg);
+  GemmW4A8GroupedArgs g{};
+  g.Aq = xq.data_ptr();
+  g.lda = (int)xq.stride(0);
+  g.xscale = xscale.data_ptr<float>();
+  g.a_rows = arp;
+  g.offsets = offsets.data_ptr<int32_t>();
+  g.w_ptrs = reinterpret_cast<const unsigned long long*>(w_ptrs.data_ptr<int64_t>());
+  g.s_ptrs = reinterpret_cast<const unsigned long long*>(s_ptrs.data_ptr<int64_t>());
+  g.R = (int)R;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.act = (int)act;
+  g.n_groups = (int)E;
+  g.config = cfg;
+  g.shared_weights = shared_weights ? 1 : 0;
+  g.store_pol = (int)store_pol;
+  g.scales_aligned4 = s_al4 ? 1 : 0;
+  if (out_ptrs.has_value()) {
+    TORCH_CHECK((int64_t)outs.size() == E && out_ptrs->is_cuda() && out_ptrs->scalar_type() == at::kLong &&
+                    out_ptrs->numel() == E,
+                "compact outputs: E tensors + int64 [E] addresses");
+    const int64_t cap = outs[0].size(0);
+    for (const auto& o : outs) {
+      check_bf16(o, "expert output");
+      TORCH_CHECK(o.dim() == 2 && o.is_contiguous() && o.size(1) == NO && o.size(0) == cap,
+                  "expert outputs: E contiguous [cap][N'] tensors");
+    }
+    g.ldc = (int)NO;
+    g.compact_rows = (int)cap;
+    g.c_ptrs = reinterpret_cast<const unsigned long long*>(out_ptrs->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(out.has_value(), "grouped GEMM needs `out` or compact outputs");
+    check_bf16(*out, "out");
+    TORCH_CHECK(out->dim() == 2 && out->stride(1) == 1, "out must be 2-D with contiguous rows");
+    TORCH_CHECK(out->size(0) == R && out->size(1) == NO, "out must be [R][N'] (N' = N/2 with SwiGLU)");
+    g.C = out->data_ptr();
+    g.ldc = (int)out->stride(0);
+  }
+  if (R == 0) return;
+  launch_gemm_w4a8_grouped(g, cur_stream());
+}
+
 // experts: list of E compact [rows][H] bf16 outputs; ptrs: int64 [E] device tensor holding
 // their addresses (built once by the caller and cached — hipGraph-safe)
 at::Tensor moe_gather_combine(const std::vector<at::Tensor>& experts, const at::Tensor& ptrs, const at::Tensor& idx,
@@ -1316,6 +1410,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_w8_grouped_num_configs", &gemm_w8_grouped_num_configs);
   m.def("gemm_w8_grouped_tile_rows", &gemm_w8_grouped_tile_rows);
   m.def("gemm_w8_grouped_pick", &gemm_w8_grouped_pick);
+  m.def("gemm_grouped_w4a8", &gemm_grouped_w4a8, py::arg("xq"), py::arg("xscale"), py::arg("weights"),
+        py::arg("scales"), py::arg("w_ptrs"), py::arg("s_ptrs"), py::arg("offsets"), py::arg("act") = 0,
+        py::arg("out") = py::none(), py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(),
+        py::arg("config") = -1, py::arg("rows_hint") = 0, py::arg("a_rows") = py::none(),
+        py::arg("shared_weights") = false, py::arg("store_pol") = 0);
+  m.def("gemm_w4a8_grouped_num_configs", &gemm_w4a8_grouped_num_configs);
+  m.def("gemm_w4a8_grouped_tile_rows", &gemm_w4a8_grouped_tile_rows);
+  m.def("gemm_w4a8_grouped_pick", &gemm_w4a8_grouped_pick);
   m.attr("REGSTAGE") = kRegStage;
   m.attr("PERSIST") = kGemmPersist;
   m.def("gemm_pick_config", &gemm_pick_config);

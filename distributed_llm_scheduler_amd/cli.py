@@ -19,11 +19,12 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
 --tp, --sp, --seed, --dtype (bf16: the kernels compute in bf16 with fp32 accumulation),
---weight-dtype {bf16,fp8,fp8-experts,mxfp4} (how GEMM weights are STORED: fp8 = e4m3 + one fp32 scale
-per output channel, dense models; fp8-experts = the same for the expert weights of an MoE model only;
-mxfp4 = OCP MXFP4, e2m1 + one e8m0 scale per 32 elements, dense models, needs --act-dtype fp8),
---act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8 or mxfp4: GEMM inputs quantised per row, multiplied
-on the block-scaled MFMA against the fp8 or fp4 weight).
+--weight-dtype {bf16,fp8,fp8-experts,mxfp4,mxfp4-experts} (how GEMM weights are STORED: fp8 = e4m3 + one
+fp32 scale per output channel, dense models; fp8-experts = the same for the expert weights of an MoE model
+only; mxfp4 = OCP MXFP4, e2m1 + one e8m0 scale per 32 elements, dense models, needs --act-dtype fp8;
+mxfp4-experts = MXFP4 for the expert weights of an MoE model only, needs --act-dtype fp8),
+--act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8, mxfp4 or mxfp4-experts: GEMM inputs quantised per row,
+multiplied on the block-scaled MFMA against the fp8 or fp4 weight).
 """
 from __future__ import annotations
 
@@ -54,16 +55,17 @@ def _common(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--dtype", default="bf16", choices=["bf16"],
                     help="compute dtype of activations and MFMA operands (bf16, fp32 accumulation); the storage of "
                          "the GEMM weights is selectable with --weight-dtype")
-    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp8-experts", "mxfp4"],
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp8-experts", "mxfp4", "mxfp4-experts"],
                     help="GEMM weight storage: bf16, or fp8 (OCP e4m3 + one fp32 scale per output channel; dense "
                          "models, no --tp / --sp): about half the parameter bytes under the same --hbm-cap-gb; "
                          "fp8-experts: the same storage for the expert weights of an MoE model (router, attention "
                          "and LM head stay bf16; no --tp / --sp); mxfp4: OCP MXFP4 for the tensors fp8 marks (e2m1 + one "
                          "e8m0 scale per 32 elements, 0.53 bytes per element; dense models, no --tp / --sp, needs "
-                         "--act-dtype fp8)")
+                         "--act-dtype fp8); mxfp4-experts: MXFP4 for the expert weights of an MoE model (router, "
+                         "attention and LM head stay bf16; no --tp / --sp, needs --act-dtype fp8)")
     ap.add_argument("--act-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="GEMM input dtype over quantised weights: bf16 (the W8A16 kernel), or fp8 (needs --weight-dtype "
-                         "fp8 or mxfp4: rows quantised to e4m3 with one power-of-two scale each, multiplied on the "
+                         "fp8, mxfp4 or mxfp4-experts: rows quantised to e4m3 with one power-of-two scale each, multiplied on the "
                          "block-scaled MFMA: W8A8 or W4A8)")
     ap.add_argument("--no-fuse", action="store_true")
 

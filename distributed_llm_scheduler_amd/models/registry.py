@@ -33,6 +33,9 @@ WEIGHT_DTYPES = ("bf16", "fp8", "fp8-experts")
 # block-scaled (OCP MX) weight storage, accepted next to WEIGHT_DTYPES: "mxfp4" marks the tensors
 # "fp8" marks (dense models) and needs act_dtype="fp8"
 MX_WEIGHT_DTYPES = ("mxfp4",)
+# the same storage for the expert weights of an MoE model only (what "fp8-experts" marks), also
+# with act_dtype="fp8": the grouped W4A8 kernel
+MX_EXPERT_WEIGHT_DTYPES = ("mxfp4-experts",)
 ACT_DTYPES = ("bf16", "fp8")
 # (op kind, weight key) pairs that read a tensor as a GEMM weight operand
 _GEMM_OPERANDS = {("linear", "w"), ("lm_head", "w"), ("attention", "w_qkv"), ("attention", "w_o"),
@@ -72,9 +75,16 @@ def mark_fp8(tasks: List[Task], groups: Dict[str, ParamGroup], operands=_GEMM_OP
 def check_act_dtype(act_dtype: str, weight_dtype: str) -> None:
     """``act_dtype="fp8"`` (e4m3 GEMM inputs, one power-of-two scale per row) exists only over
     quantised GEMM weights of a dense model: ``weight_dtype="fp8"`` (the W8A8 kernel) or
-    ``"mxfp4"`` (the W4A8 kernel, which is the only MXFP4 GEMM: ``"mxfp4"`` needs ``"fp8"``)."""
+    ``"mxfp4"`` (the W4A8 kernel, which is the only MXFP4 GEMM: ``"mxfp4"`` needs ``"fp8"``) —
+    and over the MXFP4 expert weights of an MoE model, ``weight_dtype="mxfp4-experts"`` (the grouped
+    W4A8 kernel; it needs ``"fp8"`` for the same reason)."""
     if act_dtype not in ACT_DTYPES:
         raise ValueError(f"act_dtype must be one of {ACT_DTYPES}, got {act_dtype!r}")
+    if weight_dtype in MX_EXPERT_WEIGHT_DTYPES:
+        if act_dtype != "fp8":
+            raise ValueError(f"weight_dtype={weight_dtype!r} needs act_dtype='fp8': the one grouped MXFP4 kernel is "
+                             f"W4A8 (e4m3 activation rows on the block-scaled MFMA), got act_dtype={act_dtype!r}")
+        return
     if act_dtype == "fp8" and weight_dtype not in ("fp8", "mxfp4"):
         raise ValueError(f"act_dtype='fp8' needs weight_dtype='fp8' or 'mxfp4' (the fp8 x fp8 and MXFP4 x fp8 "
                          f"GEMMs of dense models), got weight_dtype={weight_dtype!r}")
@@ -97,9 +107,13 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     not depend on it) needs ``weight_dtype="fp8"`` or ``"mxfp4"``. ``weight_dtype="mxfp4"``: the
     tensors ``"fp8"`` marks, stored as OCP MXFP4 (e2m1 pairs + one e8m0 scale per 32 elements of K,
     0.53 bytes per element); dense models only, no ``tp`` / ``sp``, every marked K a multiple of
-    32, and ``act_dtype="fp8"`` (the one kernel is W4A8)."""
-    if weight_dtype not in WEIGHT_DTYPES + MX_WEIGHT_DTYPES:
-        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES + MX_WEIGHT_DTYPES}, got {weight_dtype!r}")
+    32, and ``act_dtype="fp8"`` (the one kernel is W4A8). ``weight_dtype="mxfp4-experts"``: the
+    tensors ``"fp8-experts"`` marks, stored as MXFP4 — router, attention and LM head stay bf16; not
+    with a model without experts, ``tp`` or ``sp``; every marked K a multiple of 32, and
+    ``act_dtype="fp8"`` (the grouped kernel is W4A8)."""
+    known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
+    if weight_dtype not in known:
+        raise ValueError(f"weight_dtype must be one of {known}, got {weight_dtype!r}")
     check_act_dtype(act_dtype, weight_dtype)
     cfg = get_config(model)
     if weight_dtype == "fp8":
@@ -120,6 +134,13 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         if tp > 1 or sp > 1:
             raise ValueError("weight_dtype='fp8-experts' does not combine with tensor or sequence parallelism "
                              "(tp, sp > 1)")
+    if weight_dtype in MX_EXPERT_WEIGHT_DTYPES:
+        if not cfg.n_experts:
+            raise ValueError(f"weight_dtype={weight_dtype!r} needs an MoE model; {model} has no experts "
+                             "(weight_dtype='mxfp4' covers dense models)")
+        if tp > 1 or sp > 1:
+            raise ValueError(f"weight_dtype={weight_dtype!r} does not combine with tensor or sequence parallelism "
+                             "(tp, sp > 1)")
     tasks: List[Task] = []
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
@@ -138,4 +159,6 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         mark_fp8(tasks, groups, _EXPERT_OPERANDS)
     elif weight_dtype == "mxfp4":
         mark_fp8(tasks, groups, fmt="mxfp4")
+    elif weight_dtype in MX_EXPERT_WEIGHT_DTYPES:
+        mark_fp8(tasks, groups, _EXPERT_OPERANDS, fmt="mxfp4")
     return tasks, groups, cfg

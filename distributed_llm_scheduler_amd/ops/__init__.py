@@ -1020,6 +1020,82 @@ def gemm_grouped_w8(x, qweights, scales, offsets, act=None, out=None, outs=None,
     return gemm_grouped(x, deq, offsets, act=act, out=out, outs=outs, a_rows=a_rows)
 
 
+def w4a8_grouped_configs() -> int:
+    """Number of tile configurations of the grouped MXFP4 x fp8 GEMM (``gemm_grouped_w4a8(config=...)``)."""
+    return int(ext().gemm_w4a8_grouped_num_configs())
+
+
+def w4a8_grouped_tile_rows(config: int) -> int:
+    """Row-tile height of a grouped MXFP4 x fp8 GEMM configuration (a group of more rows takes
+    several passes of its block)."""
+    return int(ext().gemm_w4a8_grouped_tile_rows(int(config)))
+
+
+def gemm_grouped_w4a8(xq, xscale, qweights, bscales, offsets, act=None, out=None, outs=None, w_ptrs=None,
+                      s_ptrs=None, out_ptrs=None, rows_hint=None, a_rows=None, shared_weights=False, config=None):
+    """:func:`gemm_grouped` with MXFP4 expert weights and fp8 activation rows: group g computes
+    ``act(xscale[row(r)] * sum_k xq[row(r)][k] * W_g[n][k])`` over its sorted rows r, with
+    ``row(r) = a_rows[r]`` when ``a_rows`` is given, else r. ``xq`` is e4m3 [rows, K] with one
+    fp32 scale per row of ``xq`` (:func:`quantize_rows_fp8`) — with ``a_rows`` the scale is
+    gathered with its row. ``W_g[n][k] = e2m1(qweights[g][n][k]) * 2^(bscales[g][n][k/32] - 127)``
+    in the layout of :func:`quantize_mxfp4` (``q`` uint8 [N, K/2], ``s`` uint8 [N, K/32], any code
+    0..254), K % 32 == 0, fp32 accumulation, bf16 output, no bias. ``act``: ``None`` or
+    ``"swiglu"`` (rows of q AND s gate/up-interleaved in blocks of ``SWIGLU_BLOCK``, N/2 outputs).
+    Rows, ``out`` / compact ``outs``, ``shared_weights`` and the cached pointer arrays as in
+    :func:`gemm_grouped_w8`. GPU: ONE launch of gemm_w4a8_grouped.hip (the MXFP4 bytes go global ->
+    registers -> the block-scaled MFMA, which applies the e8m0 scales; no split-K, no atomics:
+    bitwise reproducible). ``config``: ``None`` picks by ``(rows_hint, N, K)``; ``c`` forces tile
+    configuration c (< :func:`w4a8_grouped_configs`). CPU tensors run :func:`gemm_grouped`'s
+    reference loop on the two dequantised operands."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if xq.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"gemm_grouped_w4a8: the activations must be float8_e4m3fn, got {xq.dtype}")
+    for q, s in zip(qweights, bscales):
+        if q.dtype != torch.uint8 or s.dtype != torch.uint8:
+            raise TypeError("gemm_grouped_w4a8: the MXFP4 weights and their block scales must be uint8, got "
+                            f"{q.dtype} and {s.dtype}")
+    if a not in (0, SWIGLU):
+        raise ValueError("gemm_grouped_w4a8: act is None or 'swiglu'")
+    E = len(qweights)
+    if E == 0 or len(bscales) != E:
+        raise ValueError("gemm_grouped_w4a8: one block-scale tensor per expert weight")
+    if xq.dim() != 2:
+        raise ValueError(f"gemm_grouped_w4a8: xq must be [rows, K], got {tuple(xq.shape)}")
+    K = xq.shape[1]
+    if K % 32 or K < 32:
+        raise ValueError(f"gemm_grouped_w4a8: K must be a multiple of 32, got {K}")
+    N = qweights[0].shape[0]
+    for q, s in zip(qweights, bscales):
+        if tuple(q.shape) != (N, K // 2) or tuple(s.shape) != (N, K // 32):
+            raise ValueError(f"gemm_grouped_w4a8: expected q [{N}, {K // 2}] and s [{N}, {K // 32}], got "
+                             f"{tuple(q.shape)} and {tuple(s.shape)}")
+    if xscale.dtype != torch.float32 or xscale.numel() != xq.shape[0]:
+        raise ValueError(f"gemm_grouped_w4a8: xscale must be fp32 with one entry per row of xq ({xq.shape[0]}), got "
+                         f"{xscale.dtype} x {xscale.numel()}")
+    R = xq.shape[0] if a_rows is None else a_rows.numel()
+    if _gpu(xq):
+        if config is not None and not 0 <= int(config) < w4a8_grouped_configs():
+            raise ValueError(f"gemm_grouped_w4a8: config must be below {w4a8_grouped_configs()}, got {config}")
+        for q in qweights:
+            if q.data_ptr() % 16:
+                raise ValueError("gemm_grouped_w4a8: the weights must be 16-byte aligned")
+        mk = lambda ts: torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=xq.device)  # noqa: E731
+        if w_ptrs is None:
+            w_ptrs = mk(qweights)
+        if s_ptrs is None:
+            s_ptrs = mk(bscales)
+        if outs is not None and out_ptrs is None:
+            out_ptrs = mk(outs)
+        ext().gemm_grouped_w4a8(xq, xscale, list(qweights), list(bscales), w_ptrs, s_ptrs, offsets, a, out,
+                                list(outs) if outs is not None else [], out_ptrs,
+                                -1 if config is None else int(config), int(rows_hint or max(1, R // E)), a_rows,
+                                bool(shared_weights), _stream_pol(N, K) & 6)
+        return out if outs is None else outs
+    xd = dequantize_fp8(xq, xscale, torch.float32)
+    deq = [dequantize_mxfp4(q, s, torch.float32) for q, s in zip(qweights, bscales)]
+    return gemm_grouped(xd, deq, offsets, act=act, out=out, outs=outs, a_rows=a_rows)
+
+
 def grouped_gemm(X, offsets, W, act=None):
     """Per-expert ``act(X_e @ W_e^T)`` over expert-sorted rows; W is [E][N][K]."""
     a = ACT[act] if not isinstance(act, int) else act

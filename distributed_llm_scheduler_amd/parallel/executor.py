@@ -266,6 +266,7 @@ class DAGExecutor:
         self._ext_stats: Dict[str, torch.Tensor] = {}   # the same buffers, by the tensor a norm reads
         self._stats_slab: Optional[torch.Tensor] = None
         self._moe_ptrs: Dict[tuple, torch.Tensor] = {}
+        self._moe_q8_bufs: Dict[tuple, tuple] = {}  # MXFP4 experts: quantised input rows + scales, per input
         self._pending_sends: Dict[int, object] = {}  # send instruction index -> RCCL work
         self._param_recv: Dict[str, object] = {}     # group -> RCCL work of its peer fill
         self._started = False
@@ -563,6 +564,14 @@ class DAGExecutor:
         if self._moe_w8(tasks):  # fp8 expert weights: the grouped W8A16 kernel, same groups and rows
             q13, s13, q2, s2 = self._moe_w8_weights(tasks)
             pt = self._moe_w8_ptrs(("x", i), q13, s13, q2, s2, outs) if self.gpu else (None,) * 5
+            if q13[0].dtype == torch.uint8:  # MXFP4: the grouped W4A8 kernel on quantised rows
+                xq, xs = self._moe_q8(("xpb",), xp)
+                ops.gemm_grouped_w4a8(xq, xs, q13, s13, offsets, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                      rows_hint=hint, a_rows=a_rows, shared_weights=True)
+                hq, hs = self._moe_q8(("h",), hbuf)
+                ops.gemm_grouped_w4a8(hq, hs, q2, s2, offsets, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                      rows_hint=hint, shared_weights=True)
+                return
             ops.gemm_grouped_w8(xp, q13, s13, offsets, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
                                 rows_hint=hint, a_rows=a_rows, shared_weights=True)
             ops.gemm_grouped_w8(hbuf, q2, s2, offsets, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
@@ -659,6 +668,16 @@ class DAGExecutor:
             q13, s13, q2, s2 = self._moe_w8_weights(tasks)
             pt = self._moe_w8_ptrs(i, q13, s13, q2, s2, outs)
             hbuf = self._scratch("moe_h", (R, F))
+            if q13[0].dtype == torch.uint8:  # MXFP4: the grouped W4A8 kernel on quantised rows
+                # (per-row quantisation commutes with the row gather: the token matrix is quantised,
+                # the kernel gathers rows and scales by src)
+                xq, xs = self._moe_q8(("in",), x)
+                ops.gemm_grouped_w4a8(xq, xs, q13, s13, off, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                      rows_hint=max(1, R // E), a_rows=rows)
+                hq, hs = self._moe_q8(("h",), hbuf)
+                ops.gemm_grouped_w4a8(hq, hs, q2, s2, off, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                      rows_hint=max(1, R // E))
+                return
             ops.gemm_grouped_w8(x, q13, s13, off, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
                                 rows_hint=max(1, R // E), a_rows=rows)
             ops.gemm_grouped_w8(hbuf, q2, s2, off, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
@@ -677,7 +696,8 @@ class DAGExecutor:
         ops.gemm_grouped(hbuf, w2, off, outs=outs, w_ptrs=cached[2], out_ptrs=cached[3], rows_hint=max(1, R // E))
 
     def _moe_w8(self, tasks) -> bool:
-        """Are these expert nodes' weights stored as fp8 (weight_dtype="fp8-experts")?"""
+        """Are these expert nodes' weights stored quantised (weight_dtype="fp8-experts": e4m3;
+        "mxfp4-experts": uint8 e2m1 pairs — the callers dispatch on the stored dtype)?"""
         return bool(self._q_names) and tasks[0].op.weights["w_gate_up"] in self._q_names
 
     def _moe_w8_weights(self, tasks):
@@ -709,6 +729,32 @@ class DAGExecutor:
             cached = (mk(q13), mk(s13), mk(q2), mk(s2), mk(outs))
             self._moe_bufs[("w8", key, ptrs)] = cached
         return cached
+
+    def _moe_q8(self, key: tuple, x: torch.Tensor, memo: Optional[tuple] = None):
+        """(e4m3 rows, fp32 row scales) of a grouped W4A8 GEMM's input matrix ``x``: one quantiser
+        launch. ``memo`` names the input: quantised once per step (like the routing) and shared by
+        every expert node that reads it; without it the matrix is quantised at each use (a batch's
+        inputs, read once). The rows and scales live in scratch of their own per ``key`` (not the
+        _a8_rows pair, which the GEMMs between a layer's expert nodes reuse), allocated in the eager
+        warm-up step only. The CPU backend lets the op allocate."""
+        k = ("q8",) + memo if memo is not None else None
+        r = self._moe_memo.get(k) if memo is not None else None
+        if r is None:
+            oq = osc = None
+            if self.gpu:
+                M, K = x.shape
+                bufs = self._moe_q8_bufs.get(key)
+                if bufs is None or bufs[0].numel() < M * K or bufs[1].numel() < M:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("MXFP4 expert activation scratch must be allocated before hipGraph capture")
+                    bufs = (torch.empty(M * K, dtype=torch.uint8, device=self.device),
+                            torch.empty(M, dtype=torch.float32, device=self.device))
+                    self._moe_q8_bufs[key] = bufs
+                oq, osc = bufs[0][:M * K].view(M, K), bufs[1][:M]
+            r = ops.quantize_rows_fp8(x, oq, osc)
+            if memo is not None:
+                self._moe_memo[k] = r
+        return r
 
     def _plan_prefetch(self) -> None:
         """For every ``load`` at instruction i: the earliest point it may start — right after
@@ -1447,6 +1493,16 @@ class DAGExecutor:
             q13, s13, q2, s2 = self._moe_w8_weights([t])
             o2 = [self._flat(out)]
             pt = self._moe_w8_ptrs(("e", t.id), q13, s13, q2, s2, o2) if self.gpu else (None,) * 5
+            if q13[0].dtype == torch.uint8:  # MXFP4: a one-group pair of the grouped W4A8 kernel
+                # the permuted rows are quantised once per step and shared by the layer's expert nodes
+                xq, xs = self._moe_q8(("perm", t.op.inputs[0].split("/")[0]), xp,
+                                      memo=("perm", t.op.inputs[0], t.op.inputs[1]))
+                ops.gemm_grouped_w4a8(xq, xs, q13, s13, rows, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                      rows_hint=hint)
+                hq, hs = self._moe_q8(("h",), hbuf)
+                ops.gemm_grouped_w4a8(hq, hs, q2, s2, rows, outs=o2, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
+                                      rows_hint=hint)
+                return
             ops.gemm_grouped_w8(xp, q13, s13, rows, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1], rows_hint=hint)
             ops.gemm_grouped_w8(hbuf, q2, s2, rows, outs=o2, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
                                 rows_hint=hint)

@@ -110,11 +110,16 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     ``"fp8"`` marks, stored as OCP MXFP4 (e2m1 pairs and one e8m0 scale per 32 elements of K:
     0.53 bytes per element); raises ``ValueError`` with an MoE model, ``tp > 1``, ``sp > 1``, a
     marked K that is no multiple of 32, or ``act_dtype != "fp8"`` (the one kernel is W4A8).
+    ``weight_dtype="mxfp4-experts"``: MXFP4 storage for the tensors ``"fp8-experts"`` marks (router,
+    attention and LM head stay bf16); raises ``ValueError`` with a model without experts,
+    ``tp > 1``, ``sp > 1``, a marked K that is no multiple of 32, or ``act_dtype != "fp8"`` (the
+    grouped kernel is W4A8).
 
-    ``act_dtype="fp8"`` (with ``weight_dtype="fp8"`` or ``"mxfp4"`` only; anything else raises
-    ``ValueError``): the input rows of every GEMM on a quantised weight are quantised to e4m3 with
-    one power-of-two scale per row and multiplied on the block-scaled MFMA (``ops.linear_w8a8`` /
-    ``ops.linear_w4a8``); the DAG, the bytes and the placement are those of the ``weight_dtype``.
+    ``act_dtype="fp8"`` (with ``weight_dtype="fp8"``, ``"mxfp4"`` or ``"mxfp4-experts"`` only;
+    anything else raises ``ValueError``): the input rows of every GEMM on a quantised weight are
+    quantised to e4m3 with one power-of-two scale per row and multiplied on the block-scaled MFMA
+    (``ops.linear_w8a8`` / ``ops.linear_w4a8`` / ``ops.gemm_grouped_w4a8``); the DAG, the bytes and
+    the placement are those of the ``weight_dtype``.
 
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
