@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""The decode step of llama3-8b-1l (one layer of Llama-3-8B at full width, LM head included) with a
+KV cache: ms per step as ONE captured hipGraph replayed over a growing sequence, the launches of
+that graph, and where the time goes — per kernel group of the program (an event pair around every
+group of an eager step; the groups are a launch or a few, so each figure carries about a
+microsecond of event overhead) — for T new tokens per step from a context of P random cache rows
+(executor.kv_randomize). The M = B*T <= 16 GEMMs run on the tiles the prefill shapes use: their
+share of the step is the baseline a GEMV path would be measured against.
+
+    python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--out FILE]
+
+Needs a GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
+
+CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, past)
+
+
+def one(model, C, B, T, past, steps=10, rounds=5):
+    dev = torch.device("cuda:0")
+    p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C)
+    ex = runtime.make_executor(p, 0, dev, runtime.make_store(p, device_init=runtime.device_init_ok(p, 0)))
+    ex.kv_randomize(past)
+    ex.step()
+    ex.kv_reset(past)
+    if not ex.capture():
+        raise RuntimeError("the decode step was not captured")
+    assert past + steps * T <= C
+    ms = []
+    for _ in range(rounds):
+        ex.kv_reset(past)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            ex.step()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b) / steps)
+    ex.kv_reset(past)
+    ex.step(profile=True)  # (leaves the graph; warms the eager path)
+    ex.kv_reset(past)
+    tl = ex.step(profile=True).timeline
+    total = sum(t1 - t0 for _, t0, t1 in tl)
+    kinds = {i.task: i.kind for i in p.programs[0].instrs if i.op == "run"}
+    lines = [f"{model}  B {B}  T {T}  past {past}  cache {C} ({sum(p.kv_cache_bytes) / 1e6:.1f} MB): "
+             f"{statistics.median(ms) * 1e3:.1f} us per step as one hipGraph of {ex.launches} kernel launches "
+             f"(min {min(ms) * 1e3:.1f}, max {max(ms) * 1e3:.1f} over {rounds} rounds of {steps} steps)",
+             f"  {'kernel group (eager, event pairs)':58s} {'us':>8s} {'share':>6s}"]
+    gemm = 0.0
+    for name, t0, t1 in tl:
+        kind = kinds.get(name, "")
+        lines.append(f"  {name + '  [' + kind + ']':58s} {(t1 - t0) * 1e3:8.1f} {(t1 - t0) / total * 100:5.1f}%")
+        if any(k in kind for k in ("linear", "lm_head", "swiglu_mlp")):
+            gemm += t1 - t0
+    attn = sum(t1 - t0 for name, t0, t1 in tl if "attention" in kinds.get(name, ""))
+    lines.append(f"  groups that are GEMMs only (MLP, LM head): {gemm / total * 100:.1f}% of the eager step; the attention "
+                 f"group (QKV GEMM, kv_append, attn_decode, out-projection): {attn / total * 100:.1f}%")
+    del ex
+    torch.cuda.empty_cache()
+    return lines
+
+
+def step_breakdown(model="llama3-8b-1l", C=8192):
+    out = []
+    for B, T, past in CASES:
+        out += one(model, C, B, T, past) + [""]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="llama3-8b-1l")
+    ap.add_argument("--kv-cache", type=int, default=8192)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("decode_step.py needs a GPU")
+    lines = step_breakdown(a.model, a.kv_cache)
+    print("\n".join(lines), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

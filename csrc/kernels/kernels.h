@@ -295,6 +295,37 @@ struct AttnArgs {
 void launch_attention_fwd(const AttnArgs& a, hipStream_t s);
 void attention_split_sizes(const AttnArgs& a, size_t* part_floats, size_t* counters);
 
+// KV cache and decode steps (attn_decode.hip). The caches are bf16 [B][C][n_kv_head*D]; pos is
+// int32 [B] in device memory (the length of every sequence before the step), so one captured
+// launch serves every step.
+struct DecodeArgs {
+  const void* q; int ldq;  // bf16 [B*T][>= n_head*D], row b*T + t, head h at column h*D
+  const void* k_cache;     // bf16 [B][C][n_kv_head*D]
+  const void* v_cache;
+  void* o; int ldo;        // bf16 [B*T][>= n_head*D]
+  const int* pos;          // int32 [B]: query t of sequence b sits at position pos[b] + t
+  int B, T, C, n_head, n_kv_head, D;
+  float scale;
+  int chunk = 0;           // keys per workgroup (a multiple of 64); 0: attn_decode_chunk()
+  void* part = nullptr;    // fp32 partials, attn_decode_sizes() floats
+  void* cnt = nullptr;     // int32 tickets, zero before the first launch (self-resetting)
+};
+// T in 1..16, (n_head / n_kv_head) * T <= 64, D 64 or 128
+bool attn_decode_supported(int T, int n_head, int n_kv_head, int D);
+// the launcher's keys per workgroup: the grid (ceil(C / chunk), n_kv_head, B) fills 256 CUs where C allows
+int attn_decode_chunk(int B, int C, int n_kv_head, int D);
+void attn_decode_sizes(const DecodeArgs& a, size_t* part_floats, size_t* counters);
+void launch_attn_decode(const DecodeArgs& a, hipStream_t s);
+// rows pos[b] .. pos[b]+T-1 of sequence b's caches = rows b*T .. b*T+T-1 of k_new / v_new
+// (bf16 [B*T][>= n_kv_head*D] views, 16-byte aligned rows); rows at or past C are dropped
+void launch_kv_append(const void* k_new, int ldk, const void* v_new, int ldv, void* k_cache, void* v_cache,
+                      const int* pos, int B, int T, int C, int row_elems, hipStream_t s);
+// tok_out[b*T + t] = tokens[b][p], out_i[b*T + t] = tab_i[p] (rows of row_bytes_i, a multiple of 16;
+// tab_i may be null) with p = min(pos[b] + t, C - 1)
+void launch_decode_prologue(const int* pos, const int* tokens, int* tok_out, const void* tab0, void* out0,
+                            int row_bytes0, const void* tab1, void* out1, int row_bytes1, int B, int T, int C,
+                            hipStream_t s);
+
 // y = LN(x [+ r]) * w + b ; if r != nullptr and sum_out != nullptr, sum_out = x + r
 void launch_layernorm(const void* x, const void* r, void* sum_out, const void* w, const void* b, void* y, int M,
                       int H, float eps, hipStream_t s);

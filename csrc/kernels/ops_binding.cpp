@@ -596,6 +596,132 @@ at::Tensor attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor&
   return o;
 }
 
+// ---- KV cache and decode steps (attn_decode.hip)
+
+void check_i32(const at::Tensor& t, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name,
+              " must be a contiguous int32 GPU tensor of ", n, " elements");
+}
+
+// caches [B][C][n_kv_head*D] bf16, contiguous
+void check_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t row_elems) {
+  for (auto* p : {&k_cache, &v_cache}) {
+    check_bf16(*p, "cache");
+    TORCH_CHECK(p->dim() == 3 && p->is_contiguous() && p->size(2) == row_elems &&
+                    reinterpret_cast<uintptr_t>(p->data_ptr()) % 16 == 0,
+                "caches must be contiguous [B][C][n_kv_head*head_dim], 16-byte aligned");
+  }
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes() && k_cache.size(1) >= 1, "k_cache and v_cache must match");
+}
+
+void kv_append(const at::Tensor& k_new, const at::Tensor& v_new, const at::Tensor& k_cache,
+               const at::Tensor& v_cache, const at::Tensor& pos, int64_t T) {
+  const int64_t B = k_cache.size(0), C = k_cache.size(1), E = k_cache.size(2);
+  check_caches(k_cache, v_cache, E);
+  TORCH_CHECK(E % 8 == 0 && T >= 1, "kv_append: cache rows must be a multiple of 8 elements, T >= 1");
+  for (auto* p : {&k_new, &v_new}) {
+    check_bf16(*p, "k/v");
+    check_rows(*p, "k/v");
+    TORCH_CHECK(p->size(0) == B * T && p->size(1) >= E, "kv_append: k/v must be [B*T][>= n_kv_head*head_dim]");
+  }
+  check_i32(pos, B, "pos");
+  TORCH_CHECK(B * T * E < (1ll << 30), "kv_append: step too large");
+  launch_kv_append(k_new.data_ptr(), (int)k_new.stride(0), v_new.data_ptr(), (int)v_new.stride(0),
+                   k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(), (int)B, (int)T, (int)C, (int)E,
+                   cur_stream());
+}
+
+DecodeArgs decode_args(int64_t B, int64_t T, int64_t C, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                       int64_t chunk) {
+  TORCH_CHECK(n_kv_head >= 1 && attn_decode_supported((int)T, (int)n_head, (int)n_kv_head, (int)head_dim),
+              "attention_decode: needs 1 <= T <= 16, (n_head / n_kv_head) * T <= 64 and head_dim 64 or 128 (T ", T,
+              ", heads ", n_head, "/", n_kv_head, ", head_dim ", head_dim, ")");
+  TORCH_CHECK(chunk >= 0 && chunk % 64 == 0, "attention_decode: chunk must be a multiple of 64");
+  TORCH_CHECK(B >= 1 && B <= 65535 && n_kv_head <= 65535 && C >= 1, "attention_decode: batch / capacity");
+  DecodeArgs a{};
+  a.B = (int)B, a.T = (int)T, a.C = (int)C, a.n_head = (int)n_head, a.n_kv_head = (int)n_kv_head;
+  a.D = (int)head_dim, a.chunk = (int)chunk;
+  return a;
+}
+
+// (partial floats, tickets) of attention_decode's workspace; the tickets are zeroed once by the caller
+std::tuple<int64_t, int64_t> attention_decode_sizes(int64_t B, int64_t T, int64_t C, int64_t n_head,
+                                                    int64_t n_kv_head, int64_t head_dim, int64_t chunk) {
+  const DecodeArgs a = decode_args(B, T, C, n_head, n_kv_head, head_dim, chunk);
+  size_t pf = 0, nc = 0;
+  attn_decode_sizes(a, &pf, &nc);
+  return {(int64_t)pf, (int64_t)nc};
+}
+
+at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                            const at::Tensor& pos, int64_t T, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                            double scale, const at::Tensor& part, const at::Tensor& cnt,
+                            const c10::optional<at::Tensor>& out, int64_t chunk) {
+  TORCH_CHECK(k_cache.dim() == 3, "caches must be [B][C][n_kv_head*head_dim]");
+  const int64_t B = k_cache.size(0), C = k_cache.size(1);
+  DecodeArgs a = decode_args(B, T, C, n_head, n_kv_head, head_dim, chunk);
+  check_caches(k_cache, v_cache, n_kv_head * head_dim);
+  check_bf16(q, "q");
+  check_rows(q, "q");
+  TORCH_CHECK(q.size(0) == B * T && q.size(1) >= n_head * head_dim, "q must be [B*T][>= n_head*head_dim]");
+  check_i32(pos, B, "pos");
+  at::Tensor o = out.has_value() ? as2d(*out) : at::empty({B * T, n_head * head_dim}, q.options());
+  check_bf16(o, "out");
+  check_rows(o, "out");
+  TORCH_CHECK(o.size(0) == B * T && o.size(1) >= n_head * head_dim, "out must be [B*T][>= n_head*head_dim]");
+  size_t pf = 0, nc = 0;
+  attn_decode_sizes(a, &pf, &nc);
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() &&
+                  part.numel() >= (int64_t)pf && reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+              "attention_decode: partials must be a contiguous 16-byte aligned fp32 GPU tensor of >= ", pf,
+              " elements");
+  TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == at::kInt && cnt.is_contiguous() && cnt.numel() >= (int64_t)nc,
+              "attention_decode: tickets must be a contiguous int32 GPU tensor of >= ", nc, " elements");
+  // the partials of one (sequence, KV head) are addressed with 32-bit buffer offsets
+  TORCH_CHECK(pf / nc * 4 < (1ull << 31), "attention_decode: partials of one KV head exceed 2 GB");
+  a.q = q.data_ptr(), a.ldq = (int)q.stride(0);
+  a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr();
+  a.o = o.data_ptr(), a.ldo = (int)o.stride(0);
+  a.pos = pos.data_ptr<int>();
+  a.scale = (float)scale;
+  a.part = part.data_ptr(), a.cnt = cnt.data_ptr();
+  launch_attn_decode(a, cur_stream());
+  return o;
+}
+
+// one launch per step: the step's token ids and its rows of up to two [C][*] position tables
+void decode_prologue(const at::Tensor& pos, const c10::optional<at::Tensor>& tokens,
+                     const c10::optional<at::Tensor>& tok_out, int64_t T, int64_t C,
+                     const std::vector<at::Tensor>& tables, const std::vector<at::Tensor>& outs) {
+  const int64_t B = pos.numel();
+  check_i32(pos, B, "pos");
+  TORCH_CHECK(B >= 1 && T >= 1 && C >= 1 && B * T < (1 << 20), "decode_prologue: B, T, C");
+  TORCH_CHECK(tokens.has_value() == tok_out.has_value(), "decode_prologue: tokens and tok_out go together");
+  if (tokens.has_value()) {
+    check_i32(*tokens, B * C, "tokens");
+    check_i32(*tok_out, B * T, "tok_out");
+  }
+  TORCH_CHECK(tables.size() == outs.size() && tables.size() <= 2, "decode_prologue: at most two tables, one out each");
+  const void* tab[2] = {nullptr, nullptr};
+  void* dst[2] = {nullptr, nullptr};
+  int rb[2] = {0, 0};
+  for (size_t i = 0; i < tables.size(); ++i) {
+    const at::Tensor &t = tables[i], &o = outs[i];
+    TORCH_CHECK(t.is_cuda() && o.is_cuda() && t.dim() == 2 && o.dim() == 2 && t.is_contiguous() && o.is_contiguous() &&
+                    t.scalar_type() == o.scalar_type() && t.size(0) >= C && o.size(0) == B * T &&
+                    t.size(1) == o.size(1),
+                "decode_prologue: table [>= C][W] and out [B*T][W] of one dtype, contiguous");
+    const int64_t bytes = t.size(1) * t.element_size();
+    TORCH_CHECK(bytes % 16 == 0 && bytes < (1 << 24) && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(o.data_ptr()) % 16 == 0,
+                "decode_prologue: table rows must be 16-byte multiples, 16-byte aligned");
+    tab[i] = t.data_ptr(), dst[i] = o.data_ptr(), rb[i] = (int)bytes;
+  }
+  launch_decode_prologue(pos.data_ptr<int>(), tokens.has_value() ? tokens->data_ptr<int>() : nullptr,
+                         tok_out.has_value() ? tok_out->data_ptr<int>() : nullptr, tab[0], dst[0], rb[0], tab[1],
+                         dst[1], rb[1], (int)B, (int)T, (int)C, cur_stream());
+}
+
 std::vector<at::Tensor> norm(const at::Tensor& x_in, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                              double eps, const c10::optional<at::Tensor>& residual, bool rms,
                              const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& sum_out) {
@@ -1438,6 +1564,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("causal") = true,
         py::arg("scale") = 0.125, py::arg("out") = py::none(), py::arg("variant") = 0, py::arg("Sq") = 0,
         py::arg("q_off") = 0, py::arg("flags") = 0);
+  m.def("kv_append", &kv_append, py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("pos"), py::arg("T"));
+  m.def("attention_decode_sizes", &attention_decode_sizes, py::arg("B"), py::arg("T"), py::arg("C"),
+        py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("chunk") = 0);
+  m.def("attention_decode_chunk", [](int64_t B, int64_t C, int64_t n_kv_head, int64_t head_dim) {
+    return (int64_t)attn_decode_chunk((int)B, (int)C, (int)n_kv_head, (int)head_dim);
+  });
+  m.def("attention_decode", &attention_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("pos"),
+        py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("scale"),
+        py::arg("part"), py::arg("cnt"), py::arg("out") = py::none(), py::arg("chunk") = 0);
+  m.def("decode_prologue", &decode_prologue, py::arg("pos"), py::arg("tokens"), py::arg("tok_out"), py::arg("T"),
+        py::arg("C"), py::arg("tables"), py::arg("outs"));
   m.def("norm", &norm, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5,
         py::arg("residual") = py::none(), py::arg("rms") = false, py::arg("out") = py::none(),
         py::arg("sum_out") = py::none());

@@ -24,7 +24,9 @@ fp32 scale per output channel, dense models; fp8-experts = the same for the expe
 only; mxfp4 = OCP MXFP4, e2m1 + one e8m0 scale per 32 elements, dense models, needs --act-dtype fp8;
 mxfp4-experts = MXFP4 for the expert weights of an MoE model only, needs --act-dtype fp8),
 --act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8, mxfp4 or mxfp4-experts: GEMM inputs quantised per row,
-multiplied on the block-scaled MFMA against the fp8 or fp4 weight).
+multiplied on the block-scaled MFMA against the fp8 or fp4 weight), --kv-cache C (decode steps: --seq is
+the number of new tokens per step and every attention node keeps a KV cache of C positions) and, for
+``run``, --past P (the caches are filled with random rows to length P before the timed steps).
 """
 from __future__ import annotations
 
@@ -67,6 +69,13 @@ def _common(ap: argparse.ArgumentParser) -> None:
                     help="GEMM input dtype over quantised weights: bf16 (the W8A16 kernel), or fp8 (needs --weight-dtype "
                          "fp8, mxfp4 or mxfp4-experts: rows quantised to e4m3 with one power-of-two scale each, multiplied on the "
                          "block-scaled MFMA: W8A8 or W4A8)")
+    ap.add_argument("--kv-cache", type=int, default=None, metavar="C",
+                    help="decode steps: --seq becomes the number of new tokens per step (1 .. 16) and every attention "
+                         "node keeps K/V caches of C positions per sequence on its GPU; the caches count against "
+                         "--hbm-cap-gb (dense gpt2 / llama models; no --tp / --sp)")
+    ap.add_argument("--past", type=int, default=0, metavar="P",
+                    help="run, with --kv-cache: every sequence starts from a context of P positions of random cache "
+                         "rows (the timed steps then run at that length without P / seq steps before them)")
     ap.add_argument("--no-fuse", action="store_true")
 
 
@@ -76,7 +85,25 @@ def _plan(a, world: int, resume: Optional[str] = None):
     return runtime.plan(a.model, world=world, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, replicas=a.replicas,
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
                         placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
-                        act_dtype=a.act_dtype)
+                        act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None))
+
+
+def _has_kv(p) -> bool:
+    """The plan has KV caches: asked of the plan's arguments, the same answer on every rank."""
+    return p.args.get("kv_cache") is not None
+
+
+def _kv_fields(a, p) -> dict:
+    """JSON fields of a plan with KV caches: the capacity, the context the run starts from, the cache bytes."""
+    if not _has_kv(p):
+        return {}
+    return {"kv_cache": a.kv_cache, "past": a.past, "kv_cache_gb": sum(p.kv_cache_bytes) / 1e9}
+
+
+def _kv_check(a, n_steps: int, what: str) -> None:
+    """--past P plus the longest run of steps between two resets must fit the cache."""
+    if a.past < 0 or a.past + n_steps * a.seq > a.kv_cache:
+        raise SystemExit(f"--past {a.past} + {n_steps} steps ({what}) x --seq {a.seq} exceeds --kv-cache {a.kv_cache}")
 
 
 def _param_gb(p) -> float:
@@ -91,6 +118,7 @@ def cmd_plan(a) -> int:
     out = {"model": a.model, "scheduler": p.scheduler_name, "world": p.world, "plan_ms": round((time.time() - t0) * 1e3, 2),
            "weight_dtype": a.weight_dtype, "act_dtype": a.act_dtype, "param_gb": _param_gb(p)}
     out.update(p.stats)
+    out.update(_kv_fields(a, p))
     print(json.dumps(out))
     if a.save:
         runtime.save_plan(p, a.save)
@@ -125,12 +153,23 @@ def cmd_run_loopback(a) -> int:
     p = _plan(a, a.loopback, resume=a.resume)
     out = {"model": a.model, "world": a.loopback, "scheduler": p.scheduler_name, "harness": "loopback",
            "transport": a.transport, "tasks_completed": p.stats["tasks_completed"],
-           "tasks_total": p.stats["tasks_total"], "device": str(dev)}
+           "tasks_total": p.stats["tasks_total"], "device": str(dev), **_kv_fields(a, p)}
+    before = None
+    if _has_kv(p):
+        # the harness never resets: its warm-up steps (and the device transport's dry step on the
+        # GPU) extend the context of --past before the timed steps do
+        dry = 1 if gpu and a.transport == "device" else 0
+        _kv_check(a, dry + a.warmup + a.steps, "dry + warm-up + timed" if dry else "warm-up + timed")
+
+        def before(exs):
+            for ex in exs:
+                ex.kv_randomize(a.past, seed=a.seed)
     try:
         from .parallel.devp2p import TIMEOUT_S
 
         run = run_loopback(p, dev, steps=a.steps, warmup=a.warmup, capture=gpu and not a.no_graph,
-                           transport=a.transport, delay_us=0.0, poison=False, p2p_timeout_s=TIMEOUT_S)
+                           transport=a.transport, delay_us=0.0, poison=False, p2p_timeout_s=TIMEOUT_S,
+                           before_steps=before)
         errs = [ex.transport_errors() for ex in run.executors]
         for ex in run.executors:
             ex.check_transport()
@@ -180,10 +219,17 @@ def cmd_run(a) -> int:
         if world > 1:
             dist.barrier()
 
+    kv = _has_kv(p)  # (every rank takes part, also one that holds no cache)
+    if kv:
+        # warm-up steps and the profiled step start from --past again, like the timed ones
+        _kv_check(a, max(a.steps, 1 if (a.warmup or a.trace or a.gantt) else 0), "timed")
+        ex.kv_randomize(a.past, seed=a.seed)
     failed: Optional[str] = None  # a device-transport wait gave up on this rank (TransportError)
     try:
         for _ in range(a.warmup):
             ex.step()
+            if kv:
+                ex.kv_reset(a.past)  # every warm-up step and the timed ones start from the same context
     except Exception as e:  # noqa: BLE001
         failed = _transport_failure(e)
         if failed is None:
@@ -217,6 +263,8 @@ def cmd_run(a) -> int:
     invalid = bool(t[1].item())
     events = None
     if (a.trace or a.gantt) and not invalid:
+        if kv:
+            ex.kv_reset(a.past)  # the profiled step sees the context the timed steps started from
         st = ex.step(profile=True)
         events = [None] * world
         if world > 1:
@@ -228,7 +276,8 @@ def cmd_run(a) -> int:
                           "tasks_completed": p.stats["tasks_completed"], "tasks_total": p.stats["tasks_total"],
                           "ms_per_step": round(float(t[0].item()), 4), "device": str(dev),
                           "p2p": getattr(ex.comm, "kind", None), "valid": not invalid,
-                          "weight_dtype": a.weight_dtype, "act_dtype": a.act_dtype, "param_gb": _param_gb(p)}))
+                          "weight_dtype": a.weight_dtype, "act_dtype": a.act_dtype, "param_gb": _param_gb(p),
+                          **_kv_fields(a, p)}))
         if events is not None:
             from .utils.tracing import chrome_trace, kernel_timeline
 

@@ -93,9 +93,65 @@ def check_act_dtype(act_dtype: str, weight_dtype: str) -> None:
                          f"activation rows on the block-scaled MFMA), got act_dtype={act_dtype!r}")
 
 
+KV_MAX_STEP = 16  # new tokens per step the decode attention kernel takes
+KV_MAX_COLS = 64  # (n_head / n_kv_head) * new tokens: its query columns per KV head
+
+
+def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: int = 1) -> None:
+    """What a KV cache of ``kv_cache`` positions with ``seq`` new tokens per step does not combine with."""
+    if not isinstance(kv_cache, int) or isinstance(kv_cache, bool) or kv_cache < 1:
+        raise ValueError(f"kv_cache must be a positive number of positions, got {kv_cache!r}")
+    if cfg.n_experts:
+        raise ValueError(f"kv_cache: MoE models ({cfg.name}) have no decode step yet (dense gpt2 / llama models only)")
+    if tp > 1 or sp > 1:
+        raise ValueError("kv_cache does not combine with tensor or sequence parallelism (tp, sp > 1): a cache "
+                         "belongs to one attention node on one GPU")
+    if kv_cache > cfg.n_positions:
+        raise ValueError(f"kv_cache={kv_cache} exceeds {cfg.name}'s {cfg.n_positions} positions")
+    if seq < 1 or seq > KV_MAX_STEP:
+        raise ValueError(f"kv_cache: seq is the number of new tokens per step, 1 .. {KV_MAX_STEP}, got {seq}")
+    if seq > kv_cache:
+        raise ValueError(f"kv_cache={kv_cache} holds less than one step of {seq} tokens")
+    rep = cfg.n_head // cfg.kv_heads
+    if rep * seq > KV_MAX_COLS:
+        raise ValueError(f"kv_cache: (n_head / n_kv_head) * seq = {rep} * {seq} exceeds the decode attention "
+                         f"kernel's {KV_MAX_COLS} query rows per KV head")
+
+
+def kv_cache_bytes(op, dtype_bytes: int = 2) -> int:
+    """Bytes of an attention node's K and V caches: 2 * B * C * n_kv_head * head_dim * dtype_bytes."""
+    a = op.attrs
+    return 2 * op.out_shape[0] * a["kv_cache"] * a["n_kv_head"] * a["head_dim"] * dtype_bytes
+
+
+def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_model: str = "bytes") -> None:
+    """In place: every attention node carries ``attrs["kv_cache"] = C``; its ``memory_required``
+    grows by its cache bytes (which persist across steps, unlike its activations, so every policy
+    sees what the node needs on its GPU); its flops count the score terms over the cache length
+    (T queries x C keys in place of the causal T x T), and under the ``bytes`` cost model its time
+    the cache bytes it streams."""
+    from .gpt2 import _roofline
+
+    for t in tasks:
+        if t.op is None or t.op.kind != "attention":
+            continue
+        t.op.attrs["kv_cache"] = int(kv_cache)
+        a = t.op.attrs
+        cache = kv_cache_bytes(t.op)
+        core_old = 2.0 * batch * a["n_head"] * seq * seq * a["head_dim"]
+        core_new = 4.0 * batch * a["n_head"] * seq * kv_cache * a["head_dim"]
+        if cost_model == "bytes":
+            # the builder's time (the roofline of the old flops and the node's other bytes) stays
+            # as a floor; the new time is the larger of it and the roofline of the new flops
+            # against the cache bytes alone, which the node streams once per step
+            t.compute_time = max(t.compute_time, _roofline(t.flops - core_old + core_new, cache))
+        t.flops = t.flops - core_old + core_new
+        t.memory_required += cache / 1e9
+
+
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
-          tp: int = 1, sp: int = 1, weight_dtype: str = "bf16",
-          act_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          tp: int = 1, sp: int = 1, weight_dtype: str = "bf16", act_dtype: str = "bf16",
+          kv_cache: "int | None" = None) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
@@ -110,7 +166,8 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     32, and ``act_dtype="fp8"`` (the one kernel is W4A8). ``weight_dtype="mxfp4-experts"``: the
     tensors ``"fp8-experts"`` marks, stored as MXFP4 — router, attention and LM head stay bf16; not
     with a model without experts, ``tp`` or ``sp``; every marked K a multiple of 32, and
-    ``act_dtype="fp8"`` (the grouped kernel is W4A8)."""
+    ``act_dtype="fp8"`` (the grouped kernel is W4A8). ``kv_cache=C``: ``seq`` is the number of new
+    tokens per step and every attention node keeps a KV cache of C positions (:func:`add_kv_cache`)."""
     known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
     if weight_dtype not in known:
         raise ValueError(f"weight_dtype must be one of {known}, got {weight_dtype!r}")
@@ -141,9 +198,13 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         if tp > 1 or sp > 1:
             raise ValueError(f"weight_dtype={weight_dtype!r} does not combine with tensor or sequence parallelism "
                              "(tp, sp > 1)")
+    if kv_cache is not None:
+        check_kv_cache(cfg, seq, kv_cache, tp, sp)
     tasks: List[Task] = []
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
+    if kv_cache is not None:
+        add_kv_cache(tasks, batch, seq, kv_cache, cost_model)
     groups = param_groups(cfg)
     if tp > 1:
         from .transforms import tensor_parallel

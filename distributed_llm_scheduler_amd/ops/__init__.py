@@ -698,6 +698,90 @@ def attention(q, k, v, B, S, n_head, n_kv_head, head_dim, causal=True, scale=Non
     return y
 
 
+# ---------------------------------------------------------- KV cache and decode steps
+# Caches are bf16 [B][C][n_kv_head*head_dim]; ``pos`` (int32 [B], on the caches' device) holds
+# every sequence's length before the step, so a captured step follows a growing sequence.
+
+DECODE_HEAD_DIMS = (64, 128)  # head_dim instances of the GPU decode attention kernel (the CPU path takes any)
+
+def kv_append(k_new, v_new, k_cache, v_cache, pos, T):
+    """Rows ``pos[b] .. pos[b]+T-1`` of sequence b's caches <- rows ``b*T .. b*T+T-1`` of
+    ``k_new`` / ``v_new`` ([B*T][>= n_kv_head*head_dim], column views of the packed qkv buffer
+    allowed). Rows at or past the capacity C are dropped."""
+    if _gpu(k_cache):
+        ext().kv_append(k_new, v_new, k_cache, v_cache, pos, int(T))
+        return
+    B, C, E = k_cache.shape
+    for b, p in enumerate(pos.tolist()):
+        n = max(0, min(T, C - p))
+        k_cache[b, p:p + n] = k_new[b * T:b * T + n, :E]
+        v_cache[b, p:p + n] = v_new[b * T:b * T + n, :E]
+
+
+def attention_decode_sizes(B, T, C, n_head, n_kv_head, head_dim, chunk=0):
+    """(fp32 partial elements, int32 tickets) of ``attention_decode``'s workspace."""
+    return ext().attention_decode_sizes(B, T, C, n_head, n_kv_head, head_dim, int(chunk))
+
+
+def attention_decode_workspace(B, T, C, n_head, n_kv_head, head_dim, device, chunk=0):
+    """The workspace of ``attention_decode``: (partials, tickets), allocated once by the caller
+    (never inside a captured step); the tickets start at zero and reset themselves. The CPU path
+    needs none."""
+    if torch.device(device).type != "cuda":
+        return None
+    pf, nc = attention_decode_sizes(B, T, C, n_head, n_kv_head, head_dim, chunk)
+    return (torch.empty(max(pf, 4), dtype=torch.float32, device=device),
+            torch.zeros(max(nc, 1), dtype=torch.int32, device=device))
+
+
+def ref_attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None):
+    """fp32: query t of sequence b (row b*T + t of q) attends cache rows 0 .. pos[b]+t."""
+    B, C, _E = k_cache.shape
+    out = torch.zeros(B * T, n_head * head_dim, dtype=q.dtype, device=q.device)
+    for b, p in enumerate(pos.tolist()):
+        S = min(p + T, C)
+        out[b * T:(b + 1) * T] = ref_attention(q[b * T:(b + 1) * T], k_cache[b, :S], v_cache[b, :S], 1, S, n_head,
+                                               n_kv_head, head_dim, True, scale, Sq=T, q_off=p)
+    return out
+
+
+def attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None, out=None,
+                     workspace=None, chunk=0):
+    """Causal attention of the T new queries of every sequence (q [B*T][>= n_head*head_dim])
+    against its cache rows ``0 .. pos[b]+t``; runs after ``kv_append``. GPU: attn_decode.hip with
+    ``workspace`` from ``attention_decode_workspace`` (``chunk``: keys per workgroup, 0 = the
+    launcher's choice; the workspace must be sized with the same value). CPU: fp32 torch."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    if _gpu(q):
+        if workspace is None:
+            raise ValueError("attention_decode needs the workspace of attention_decode_workspace on the GPU")
+        return ext().attention_decode(q, k_cache, v_cache, pos, int(T), n_head, n_kv_head, head_dim, float(scale),
+                                      workspace[0], workspace[1], out, int(chunk))
+    if not (1 <= T <= 16 and n_head % n_kv_head == 0 and n_head // n_kv_head * T <= 64):  # (any head_dim here)
+        raise RuntimeError("attention_decode: needs 1 <= T <= 16 and (n_head / n_kv_head) * T <= 64 "
+                           f"(T {T}, heads {n_head}/{n_kv_head})")
+    y = ref_attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale)
+    if out is not None:
+        out[:, :n_head * head_dim].copy_(y)
+        return out
+    return y
+
+
+def decode_prologue(pos, T, C, tokens=None, tok_out=None, tables=(), outs=()):
+    """One launch per step: ``tok_out[b*T + t] = tokens[b][p]`` and ``outs[i][b*T + t] =
+    tables[i][p]`` at ``p = min(pos[b] + t, C - 1)``. ``tokens`` int32 [B][C]; ``tables`` up to
+    two [>= C][W] tables (wpe; RoPE cos and sin). The gathered rows then serve ``embedding``,
+    ``rope_`` and the GEMM's RoPE epilogue with ``S = B*T``, where ``row % S`` is the row."""
+    if _gpu(pos):
+        ext().decode_prologue(pos, tokens, tok_out, int(T), int(C), list(tables), list(outs))
+        return
+    p = (pos.long()[:, None] + torch.arange(T)[None, :]).clamp(0, C - 1)  # [B][T]
+    if tokens is not None:
+        tok_out.copy_(tokens.reshape(-1, C).gather(1, p).reshape(-1))
+    for t, o in zip(tables, outs):
+        o.copy_(t[p.reshape(-1)])
+
+
 def gelu(x, out=None):
     if _gpu(x):
         return ext().gelu(x.contiguous(), out)

@@ -176,6 +176,11 @@ ATTN_BLOCK = os.environ.get("DLS_ATTN_BLOCK", "0") == "1"
 P2P_CHECK_EVERY = max(1, int(os.environ.get("DLS_P2P_CHECK_EVERY", "8")))
 
 
+def _kv_prefix(tid: str) -> str:
+    """Request prefix of a task id (``"r3/"``, or ``""``): the key of its KV state."""
+    return tid.rsplit("/", 1)[0] + "/" if "/" in tid else ""
+
+
 class TransportError(RuntimeError):
     """A device-transport wait gave up after DLS_P2P_TIMEOUT_S (devp2p.py): the wait stopped
     spinning and the step went on, so this rank's outputs of that step are wrong."""
@@ -382,6 +387,7 @@ class DAGExecutor:
         if POST_NORM not in ("0", False) and self._copy_stream is None:
             self._plan_post_norm()  # (pairs are adjacent runs: no p2p between producer and consumer)
         self._plan_mlp_fused()
+        self._setup_kv()
 
     def _plan_post_norm(self) -> None:
         """Pair each norm that the next group would run as its own pass (its width is above
@@ -1543,7 +1549,18 @@ class DAGExecutor:
             return False
         return ops.attn_block_ok(x.shape[0], x.shape[-1], B, S, a["n_head"], a["n_kv_head"], a["head_dim"])
 
-    def _run_group(self, ins) -> None:
+    def _run_group(self, i: int, ins) -> None:
+        """One kernel group. With KV caches (_setup_kv) the first group of a request on this rank
+        also gathers the step's tokens and position-table rows at ``pos`` (one launch), and its
+        last group that reads ``pos`` advances it by T — inside the group, so a captured step or
+        segment replays both."""
+        for st in self._kv_first.get(i, ()):
+            self._kv_prologue(st)
+        self._run_group_body(ins)
+        for st in self._kv_last.get(i, ()):
+            st["pos"].add_(st["T"])
+
+    def _run_group_body(self, ins) -> None:
         grp = [self.tasks[t] for t in ins.group]
         norm = None
         if len(grp) > 1 and grp[0].op.kind in ("layernorm", "rmsnorm"):
@@ -1565,6 +1582,9 @@ class DAGExecutor:
             tok = self._x(head.op.inputs[0])
             B, S = head.op.out_shape[0], head.op.out_shape[1]
             wpe = self._w(W["wpe"]) if "wpe" in W else None
+            st = self._kv.get(_kv_prefix(head.id)) if self._kv else None
+            if st is not None:  # decode step: the tokens and wpe rows gathered at pos, one row each
+                tok, wpe, S = st["tok_g"], st["wpe_g"], B * S
             if "seq_chunk" in a:  # sequence chunk c: its token slice, positions from c*S on
                 c, P = a["seq_chunk"]
                 tok = tok.view(B, S * P)[:, c * S:(c + 1) * S]
@@ -1606,6 +1626,21 @@ class DAGExecutor:
             width = (nh + 2 * nkv) * D
             qkv = self._ws(0, (M, width))
             o = self._ws(M * width, (M, nh * D))
+            if "kv_cache" in a:
+                # decode step: QKV of the T new tokens (RoPE from the table rows gathered at pos:
+                # with S = M the kernels' row % S is the row), append, attend the caches, project
+                st = self._kv[_kv_prefix(head.id)]
+                kc, vc = self._kv_cache[head.id]
+                if a.get("rope"):
+                    self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv,
+                               rope=(st["cos_g"], st["sin_g"], M, D, (nh + nkv) * D), rope_perm=(nh, nkv, D))
+                else:
+                    self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv)
+                ops.kv_append(qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], kc, vc, st["pos"], S)
+                ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, workspace=self._kv_ws)
+                self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
+                             post_norm=self._post_norm_out(self._flat(out)))
+                return
             if self._attn_block_ok(head, norm, x, residual, out, B, S):
                 W1, cs, bd = self._prep(W["w_qkv"], norm, W.get("b_qkv"))
                 if self._attn_sync is None:  # (first, eager step: never allocated during capture)
@@ -2066,7 +2101,7 @@ class DAGExecutor:
             self._pn = self._pn_given = None
 
     def _issue_run_body(self, i: int, ins, stats: StepStats, events) -> None:
-        run = self._run_group
+        run = lambda _ins, _i=i: self._run_group(_i, _ins)  # noqa: E731
         if i in self._moe_batch:  # the layer's experts in one grouped launch pair
             run = lambda _ins, _i=i: self._run_moe_batch(_i, stats)  # noqa: E731
         elif i in self._xbatch:  # the layer's experts here over every request: one launch pair
@@ -2134,6 +2169,8 @@ class DAGExecutor:
         it eagerly with a timestamp pair around every instruction and fills
         ``stats.timeline`` (kernel groups) and ``stats.events`` (kernels, parameter fills,
         p2p sends/recvs), in ms from the step start."""
+        if self._kv and not self._kv_hold:
+            self._kv_consume()  # raises before anything is launched when a sequence would pass C
         if self._fast is not None and not profile:  # a captured whole step: one graph launch
             self._fast[0](self._fast[1], self._fast[2])
             if self._mlp_fused:
@@ -2274,8 +2311,10 @@ class DAGExecutor:
         finite (a kernel writing past its planned region or producing NaN fails loudly)."""
         if self.gpu:
             self._sync()
-        for name, full in (("activation", self._act_full), ("parameter", self._param_full),
-                           ("workspace", self._ws_full)):
+        slabs = [("activation", self._act_full), ("parameter", self._param_full), ("workspace", self._ws_full)]
+        if self._kv_full is not None:
+            slabs.append(("KV cache", self._kv_full))
+        for name, full in slabs:
             tail = full[-GUARD_BYTES:]
             if not bool((tail == GUARD_VALUE).all()):
                 raise RuntimeError(f"rank {self.prog.rank}: {name} arena guard overwritten (out-of-bounds write)")
@@ -2301,9 +2340,29 @@ class DAGExecutor:
 
     def capture(self) -> bool:
         """Capture the steady-state step into a hipGraph: the whole step for a comm-free
-        program without copy-stream refills, else its kernel-group segments (capture_segments)."""
+        program without copy-stream refills, else its kernel-group segments (capture_segments).
+        With KV caches the steps a capture runs to warm up leave no trace: the positions are put
+        back afterwards (the cache rows they wrote lie past them, where every mask hides them and
+        the next step writes again)."""
         if not self.use_graph:
             return False
+        if not self._kv:
+            return self._capture()
+        saved = {k: (st["pos"].clone() if st["pos"] is not None else None, list(st["len"]))
+                 for k, st in self._kv.items()}
+        self._kv_hold = True
+        try:
+            return self._capture()
+        finally:
+            self._kv_hold = False
+            self._sync()
+            for k, (pos, lens) in saved.items():
+                if pos is not None:
+                    self._kv[k]["pos"].copy_(pos)
+                self._kv[k]["len"] = lens
+            self._sync()
+
+    def _capture(self) -> bool:
         self._drop_runner()  # its hipGraphExec handles belong to the graphs a re-capture replaces
         self._fast = None
         if self._device_p2p and self._copy_stream is not None:
@@ -2661,5 +2720,192 @@ class DAGExecutor:
         return False
 
     def memory_bytes(self) -> Dict[str, int]:
-        return {"activations": self.act_slab.numel(), "params": self.param_slab.numel(),
-                "workspace": self.ws_slab.numel()}
+        m = {"activations": self.act_slab.numel(), "params": self.param_slab.numel(),
+             "workspace": self.ws_slab.numel()}
+        if self._kv_full is not None:
+            m["kv_cache"] = sum(k.numel() * 4 for k, _ in self._kv_cache.values())  # K and V, bf16
+            m["kv_slab"] = self.kv_slab.numel()
+        return m
+
+    # ------------------------------------------------------------- KV caches and decode steps
+    def _setup_kv(self) -> None:
+        """State of decode steps (runtime.plan kv_cache=C): a fourth slab next to the activation,
+        parameter and workspace slabs holds, for the requests this rank runs tasks of, ``pos``
+        (int32 [B], each sequence's length, advanced on the device), the token stream [B][C] where
+        the rank embeds, the step's gathered tokens / wpe / RoPE rows, the decode workspace, and
+        the K and V caches [B][C][n_kv_head*D] of the attention tasks it runs — all allocated
+        here, nothing during a step or a capture.
+
+        Whether the plan has a cache is read from the whole DAG, and every rank keeps the host
+        lengths of every request, also a rank that runs no embedding or attention task and so
+        holds no device state: the KV interface works on all ranks alike, and a step past the
+        capacity raises on all of them, not on some while the others wait for their edges."""
+        self._kv: Dict[str, dict] = {}
+        self._kv_cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._kv_first: Dict[int, list] = {}  # index in prog.instrs -> states whose prologue runs before it
+        self._kv_last: Dict[int, list] = {}  # ... -> states whose pos advances after it
+        self._kv_full = self.kv_slab = self._kv_ws = None
+        self._kv_hold = False
+        self.kv_capacity: Optional[int] = None
+        cached = [t for t in self.tasks.values() if t.op is not None and t.op.kind == "attention"
+                  and "kv_cache" in t.op.attrs]
+        if not cached:
+            return
+        C = self.kv_capacity = int(cached[0].op.attrs["kv_cache"])
+        if self.gpu:
+            # a plan says nothing about the device it will run on, so this is refused here, on
+            # every rank, before anything is allocated — not by the binding in the first step
+            bad = sorted({t.op.attrs["head_dim"] for t in cached} - set(ops.DECODE_HEAD_DIMS))
+            if bad:
+                raise ValueError(f"kv_cache: the decode attention kernel takes head_dim "
+                                 f"{' or '.join(map(str, ops.DECODE_HEAD_DIMS))}, this model has {bad[0]}; "
+                                 f"such a plan runs on the CPU executor only")
+        for t in self.tasks.values():  # host state of every request of the plan
+            if t.op is not None and t.op.kind in ("embedding", "attention") and _kv_prefix(t.id) not in self._kv:
+                B, T = t.op.out_shape[0], t.op.out_shape[1]
+                self._kv[_kv_prefix(t.id)] = dict(prefix=_kv_prefix(t.id), B=B, T=T, len=[0] * B, pos=None,
+                                                  tokens=None, tok_g=None, wpe_g=None, wpe=None, cos=None,
+                                                  sin=None, cos_g=None, sin_g=None, input=None)
+        need, ws_need = [], [0, 0]  # (state / cache key, field, bytes) in slab order
+
+        def want(key, field, shape, dtype):
+            need.append((key, field, shape, dtype, math.prod(shape) * torch.empty(0, dtype=dtype).element_size()))
+
+        last: Dict[str, int] = {}
+        for i, ins in enumerate(self.prog.instrs):
+            if ins.op != "run":
+                continue
+            for tid in ins.group:
+                t = self.tasks[tid]
+                kind = t.op.kind
+                if kind not in ("embedding", "attention"):
+                    continue
+                pre = _kv_prefix(tid)
+                B, T = t.op.out_shape[0], t.op.out_shape[1]
+                st = self._kv[pre]
+                if pre not in last:  # the device state of a request this rank runs tasks of
+                    want(pre, "pos", (B,), torch.int32)
+                    self._kv_first.setdefault(i, []).append(st)
+                last[pre] = i
+                a = t.op.attrs
+                if kind == "embedding":
+                    st["input"] = t.op.inputs[0]
+                    want(pre, "tokens", (B, C), torch.int32)
+                    want(pre, "tok_g", (B * T,), torch.int32)
+                    if "wpe" in t.op.weights:
+                        st["wpe"] = t.op.weights["wpe"]
+                        want(pre, "wpe_g", (B * T, t.op.out_shape[-1]), self.dtype)
+                else:
+                    nh, nkv, D = a["n_head"], a["n_kv_head"], a["head_dim"]
+                    if a.get("rope") and st["cos"] is None:
+                        st["cos"], st["sin"] = self._rope_tables(C, D, a.get("rope_theta", 10000.0))
+                        want(pre, "cos_g", (B * T, D // 2), torch.float32)
+                        want(pre, "sin_g", (B * T, D // 2), torch.float32)
+                    want(tid, "k", (B, C, nkv * D), self.dtype)
+                    want(tid, "v", (B, C, nkv * D), self.dtype)
+                    if self.gpu:
+                        pf, nc = ops.attention_decode_sizes(B, T, C, nh, nkv, D)
+                        ws_need = [max(ws_need[0], pf), max(ws_need[1], nc)]
+        for pre, i in last.items():
+            self._kv_last.setdefault(i, []).append(self._kv[pre])
+        if not need:
+            return  # no embedding or attention task here: the host lengths are all this rank keeps
+        if self.gpu:
+            need.append(("@ws", "part", (max(ws_need[0], 4),), torch.float32, max(ws_need[0], 4) * 4))
+            need.append(("@ws", "cnt", (max(ws_need[1], 1),), torch.int32, max(ws_need[1], 1) * 4))
+        al = lambda n: (n + 255) // 256 * 256  # noqa: E731
+        g = GUARD_BYTES if self.debug else 0
+        total = sum(al(n[4]) for n in need)
+        self._kv_full = torch.zeros(total + g, dtype=torch.uint8, device=self.device)
+        self.kv_slab = self._kv_full[:total]
+        if g:
+            self._kv_full[-g:].fill_(GUARD_VALUE)
+        off, ws, caches = 0, {}, {}
+        for key, fld, shape, dtype, nbytes in need:
+            v = self.kv_slab[off:off + nbytes].view(dtype).view(shape)
+            off += al(nbytes)
+            if key == "@ws":
+                ws[fld] = v
+            elif fld in ("k", "v"):
+                caches.setdefault(key, {})[fld] = v
+            else:
+                self._kv[key][fld] = v
+        self._kv_cache = {tid: (c["k"], c["v"]) for tid, c in caches.items()}
+        self._kv_ws = (ws["part"], ws["cnt"]) if ws else None
+        vocab = self.cfg.vocab_size if self.cfg is not None else 50257
+        for st in self._kv.values():
+            if st["tokens"] is not None:  # the default stream: C synthetic tokens per sequence
+                st["tokens"].copy_(synthetic_tokens(st["input"], st["B"] * C, vocab, self.seed).view(st["B"], C))
+
+    def _kv_prologue(self, st: dict) -> None:
+        tables, outs = [], []
+        if st["wpe_g"] is not None:
+            tables.append(self._w(st["wpe"]))
+            outs.append(st["wpe_g"])
+        if st["cos_g"] is not None:
+            tables += [st["cos"], st["sin"]]
+            outs += [st["cos_g"], st["sin_g"]]
+        if st["tokens"] is None and not tables:
+            return  # (a GPT-2 rank without the embedding: pos is all its attention needs)
+        ops.decode_prologue(st["pos"], st["T"], self.kv_capacity, st["tokens"], st["tok_g"], tables, outs)
+
+    def _kv_consume(self) -> None:
+        """Host side of a step: every sequence advances by T; one that would pass C raises here,
+        before anything is launched. The lengths advance before the step is issued, so after a
+        step that raised while it ran (a transport error, say) they are ahead of the device's
+        ``pos`` by up to T: ``kv_reset()`` brings the two together again."""
+        for st in self._kv.values():
+            if max(st["len"]) + st["T"] > self.kv_capacity:
+                raise RuntimeError(f"rank {self.prog.rank}: a step of {st['T']} tokens would take a sequence of "
+                                   f"request {st['prefix'] or '0'!r} past the KV cache capacity "
+                                   f"{self.kv_capacity} (lengths {st['len']}); kv_reset() starts over")
+        for st in self._kv.values():
+            st["len"] = [n + st["T"] for n in st["len"]]
+
+    def _kv_need(self) -> None:
+        if self.kv_capacity is None:  # asked of the plan, not of what this rank happens to hold
+            raise RuntimeError("this plan has no KV cache (runtime.plan kv_cache=C)")
+
+    def kv_lengths(self):
+        """Host copy of the sequence lengths: [B] ints, or {request prefix: [B]} with several
+        requests. The same on every rank, whether it holds a cache or not."""
+        self._kv_need()
+        out = {k: list(st["len"]) for k, st in self._kv.items()}
+        return out[""] if list(out) == [""] else out
+
+    def kv_reset(self, lengths=None) -> None:
+        """Set every sequence's length (default 0; an int, or [B] ints per request). Cache bytes
+        stay: rows at or past a sequence's length are masked and rewritten by later steps. Call it
+        on every rank alike; a rank without a cache only notes the lengths."""
+        self._kv_need()
+        if self.gpu:
+            self._sync()
+        for st in self._kv.values():
+            lens = [int(lengths or 0)] * st["B"] if lengths is None or isinstance(lengths, int) \
+                else [int(x) for x in lengths]
+            if len(lens) != st["B"] or min(lens) < 0 or max(lens) > self.kv_capacity:
+                raise ValueError(f"kv_reset: {st['B']} lengths in 0 .. {self.kv_capacity} wanted, got {lengths!r}")
+            st["len"] = lens
+            if st["pos"] is not None:  # (None: this rank runs no task of the request that reads pos)
+                st["pos"].copy_(torch.tensor(lens, dtype=torch.int32))
+
+    def set_tokens(self, name: str, tokens) -> None:
+        """The token stream [B][C] of external input ``name`` (e.g. ``"@tokens"``): step n consumes
+        columns ``len .. len+T-1`` of every sequence. A rank that does not embed ``name`` ignores it."""
+        self._kv_need()
+        for st in self._kv.values():
+            if st["input"] == name and st["tokens"] is not None:
+                t = torch.as_tensor(tokens).to(torch.int32)
+                if tuple(t.shape) != tuple(st["tokens"].shape):
+                    raise ValueError(f"set_tokens: {tuple(st['tokens'].shape)} token ids wanted, got {tuple(t.shape)}")
+                st["tokens"].copy_(t)
+
+    def kv_randomize(self, lengths, seed: int = 0) -> None:
+        """Fill the caches with seeded bf16 N(0,1) rows and set the lengths: a context of P tokens
+        without P/T steps (benchmarks; weights and tokens are synthetic anyway)."""
+        self._kv_need()
+        for tid in sorted(self._kv_cache):
+            g = torch.Generator(device=self.device).manual_seed((zlib.crc32(tid.encode()) ^ seed) & 0x7FFFFFFF)
+            for c in self._kv_cache[tid]:
+                c.normal_(generator=g)
+        self.kv_reset(lengths)

@@ -42,6 +42,9 @@ class Plan:
     # rows lo, hi) and merged token input -> the requests' token inputs, in row order
     requests: Dict = field(default_factory=dict)
     input_parts: Dict = field(default_factory=dict)
+    # plan(kv_cache=C): bytes of the KV caches of the attention tasks each rank runs (they persist
+    # across steps, next to the parameter and activation arenas); [] without a cache
+    kv_cache_bytes: List[int] = field(default_factory=list)
 
     def owner(self, tid: str) -> Optional[int]:
         """Rank holding task ``tid``'s output (a merged request resolves to its group)."""
@@ -67,7 +70,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          node_speeds: Optional[Sequence[float]] = None, link_bw_gbps: float = 153.0,
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
-         act_dtype: str = "bf16") -> Plan:
+         act_dtype: str = "bf16", kv_cache: Optional[int] = None) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -121,6 +124,22 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     (``ops.linear_w8a8`` / ``ops.linear_w4a8`` / ``ops.gemm_grouped_w4a8``); the DAG, the bytes and
     the placement are those of the ``weight_dtype``.
 
+    ``kv_cache=C``: decode steps. ``seq`` becomes the number of new tokens per step, T (a prefill
+    chunk at T = 16, decode at T = 1); every attention node keeps K/V caches of C positions per
+    sequence on the GPU it runs on (``attrs["kv_cache"]``), appends the step's T rows and attends
+    them against the cache (``ops.kv_append`` / ``ops.attention_decode``). The cache bytes,
+    ``2 * batch * C * n_kv_head * head_dim * 2`` per attention node, are part of the node's
+    ``memory_required``, and after placement parameter arena + activation arena + caches are
+    checked against every GPU's cap. A policy budgets parameters against the whole cap and sees a
+    cache only while its attention task runs, so where the check fails the DAG is placed once more
+    with every GPU's caches and activation arena set aside (a capped plan then evicts and
+    re-fills parameters around its caches); if that does not fit either — the caches alone pass
+    the cap — ``ValueError`` names the GPU and the three figures. ``Plan.kv_cache_bytes`` reports
+    the caches per rank. gpt2 and llama families, placements ``scheduler`` / ``replica`` / ``pipeline``, any
+    ``world``. Raises ``ValueError`` with an MoE model, ``tp``, ``sp`` or ``merge_mb`` above 1,
+    C above the model's positions, T above 16, ``(n_head / n_kv_head) * T`` above 64, and with
+    ``DLS_ATTN_BLOCK=1`` (the one-launch attention block has no cache).
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -139,6 +158,16 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
         args["weight_dtype"] = weight_dtype
     if act_dtype != "bf16":  # (validated by registry.build below)
         args["act_dtype"] = act_dtype
+    if kv_cache is not None:  # (validated by registry.build below)
+        args["kv_cache"] = kv_cache
+        if merge_mb > 1:
+            raise ValueError("kv_cache does not combine with merged micro-batches (merge_mb > 1): every request "
+                             "keeps caches and a position of its own")
+        if os.environ.get("DLS_ATTN_BLOCK", "0") == "1":
+            raise ValueError("kv_cache does not combine with DLS_ATTN_BLOCK=1: the one-launch attention block "
+                             "has no KV cache")
+        if placement not in ("scheduler", "replica", "pipeline"):
+            raise ValueError(f"kv_cache: placement must be 'scheduler', 'replica' or 'pipeline', got {placement!r}")
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -153,67 +182,102 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
             for j, k in enumerate(members):
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
-                                        sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype)
+                                        sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
-    nodes = [Node(f"gpu{r}", caps_gb[r], (node_speeds[r] if node_speeds else 1.0), device=r) for r in range(world)]
-    node_rank = {n.id: r for r, n in enumerate(nodes)}
-    cls = get_scheduler(scheduler)
-    kw = {}
-    if cost_model == "bytes":
-        kw["param_cost"] = {pid: b / 1e9 for pid, b in param_bytes.items()}
-    if cls.__name__ == "EFTScheduler":
-        kw["link_bw_gbps"] = link_bw_gbps
-        kw["refill_gb"] = {pid: b / 1e9 for pid, b in param_bytes.items()}  # what a refill really moves
-        # the steady-state model needs real seconds, not abstract constants: the per-task kernel
-        # times measured on an MI355X (ops/task_times.json, as the pipeline balancer uses) where
-        # the table has the model, the roofline estimate elsewhere
-        measured = measured_task_times(task_times_key(cfg.name, seq, mb_batch))
-        if measured or cost_model != "bytes":
-            kw["real_time"] = {t.id: measured.get(_base_id(t.id), real_time_s(t, param_bytes)) for t in tasks}
-    sched = cls([n.fresh() for n in nodes], **kw)
-    for t in tasks:
-        sched.add_task(t.clone())
-    if resume is not None:
-        sched, schedule = _resume(resume, args, sched)
-    elif placement == "scheduler":
-        schedule = sched.schedule()
-    elif placement in ("replica", "pipeline", "tensor", "sequence", "expert"):
-        stage_of = None
-        if placement == "pipeline" and world > 1 and os.environ.get("DLS_PIPELINE_STAGES", "balanced") != "layers":
-            stage_of = pipeline_stages(tasks, world, param_bytes, caps_gb, node_speeds, n_req,
-                                       task_times_key(cfg.name, seq, mb_batch))
-        order_in = tasks
-        if placement == "expert" and world > 1 and n_req > 1:
-            order_in = _interleave_requests(tasks)  # every GPU steps through the layers together
-        schedule = _fixed_schedule(order_in, world, sched, placement, cfg, stage_of)
-    else:
-        raise ValueError(f"unknown placement {placement!r}")
-    place = {tid: node_rank[sched.tasks[tid].assigned_node] for tid in sched.completed_tasks}
-    order = [item for _, act, _, item in sched.events if act == "RUN"]
-    caps = {r: int(caps_gb[r] * 1e9) for r in range(world)}
-    residency = residency or os.environ.get("DLS_RESIDENCY", "auto")
-    if residency not in ("auto", "trace"):
-        raise ValueError(f"unknown residency {residency!r}")
-    planned = None
-    if residency == "auto" and getattr(sched, "cyclic", False):
-        # EFT's memory model is the repeating step: its residency may be the planned keep set
-        # (program.plan_keep_sets) under the same budget the policy accounted: the node cap
-        # minus the largest activation requirement among the node's tasks
-        tmem = {t.id: t.memory_required for t in tasks}
-        budget = {r: caps_gb[r] - max([tmem[tid] for tid, rr in place.items() if rr == r] or [0.0])
-                  for r in range(world)}
-        planned = (budget, {pid: sched.param_size(pid) for pid in param_bytes})
-    prefetch = os.environ.get("DLS_PREFETCH", "auto")  # executor.PREFETCH
-    programs = build_steady_programs(tasks, place, order, world, param_bytes, caps, events=sched.events,
-                                     node_rank=node_rank, fuse=fuse, planned=planned,
-                                     lookahead=0 if prefetch == "0" else 1, force_ahead=prefetch == "1")
-    if world > 1 and os.environ.get("DLS_PEER_FILL", "1") != "0":
-        plan_peer_fills(programs, tasks, param_bytes)  # refills from a peer's HBM over xGMI
-    name = cls.name if placement == "scheduler" else placement
-    p = Plan(model, tasks, groups, cfg, name, sched, schedule, place, order, node_rank, programs, param_bytes,
-             world, cap_gb, args=args, requests=requests, input_parts=input_parts)
+
+    def place_under(caps_now: Sequence[float]) -> Plan:
+        """Run the policy (or the fixed placement, or the saved decision) under these per-GPU caps and lower it."""
+        nodes = [Node(f"gpu{r}", caps_now[r], (node_speeds[r] if node_speeds else 1.0), device=r) for r in range(world)]
+        node_rank = {n.id: r for r, n in enumerate(nodes)}
+        cls = get_scheduler(scheduler)
+        kw = {}
+        if cost_model == "bytes":
+            kw["param_cost"] = {pid: b / 1e9 for pid, b in param_bytes.items()}
+        if cls.__name__ == "EFTScheduler":
+            kw["link_bw_gbps"] = link_bw_gbps
+            kw["refill_gb"] = {pid: b / 1e9 for pid, b in param_bytes.items()}  # what a refill really moves
+            # the steady-state model needs real seconds, not abstract constants: the per-task kernel
+            # times measured on an MI355X (ops/task_times.json, as the pipeline balancer uses) where
+            # the table has the model, the roofline estimate elsewhere
+            measured = measured_task_times(task_times_key(cfg.name, seq, mb_batch))
+            if measured or cost_model != "bytes":
+                kw["real_time"] = {t.id: measured.get(_base_id(t.id), real_time_s(t, param_bytes)) for t in tasks}
+        sched = cls([n.fresh() for n in nodes], **kw)
+        for t in tasks:
+            sched.add_task(t.clone())
+        if resume is not None:
+            sched, schedule = _resume(resume, args, sched)
+        elif placement == "scheduler":
+            schedule = sched.schedule()
+        elif placement in ("replica", "pipeline", "tensor", "sequence", "expert"):
+            stage_of = None
+            if placement == "pipeline" and world > 1 and os.environ.get("DLS_PIPELINE_STAGES", "balanced") != "layers":
+                stage_of = pipeline_stages(tasks, world, param_bytes, caps_now, node_speeds, n_req,
+                                           task_times_key(cfg.name, seq, mb_batch))
+            order_in = tasks
+            if placement == "expert" and world > 1 and n_req > 1:
+                order_in = _interleave_requests(tasks)  # every GPU steps through the layers together
+            schedule = _fixed_schedule(order_in, world, sched, placement, cfg, stage_of)
+        else:
+            raise ValueError(f"unknown placement {placement!r}")
+        place = {tid: node_rank[sched.tasks[tid].assigned_node] for tid in sched.completed_tasks}
+        order = [item for _, act, _, item in sched.events if act == "RUN"]
+        caps = {r: int(caps_now[r] * 1e9) for r in range(world)}
+        mode = residency or os.environ.get("DLS_RESIDENCY", "auto")
+        if mode not in ("auto", "trace"):
+            raise ValueError(f"unknown residency {mode!r}")
+        planned = None
+        if mode == "auto" and getattr(sched, "cyclic", False):
+            # EFT's memory model is the repeating step: its residency may be the planned keep set
+            # (program.plan_keep_sets) under the same budget the policy accounted: the node cap
+            # minus the largest activation requirement among the node's tasks
+            tmem = {t.id: t.memory_required for t in tasks}
+            budget = {r: caps_now[r] - max([tmem[tid] for tid, rr in place.items() if rr == r] or [0.0])
+                      for r in range(world)}
+            planned = (budget, {pid: sched.param_size(pid) for pid in param_bytes})
+        prefetch = os.environ.get("DLS_PREFETCH", "auto")  # executor.PREFETCH
+        programs = build_steady_programs(tasks, place, order, world, param_bytes, caps, events=sched.events,
+                                         node_rank=node_rank, fuse=fuse, planned=planned,
+                                         lookahead=0 if prefetch == "0" else 1, force_ahead=prefetch == "1")
+        if world > 1 and os.environ.get("DLS_PEER_FILL", "1") != "0":
+            plan_peer_fills(programs, tasks, param_bytes)  # refills from a peer's HBM over xGMI
+        name = cls.name if placement == "scheduler" else placement
+        return Plan(model, tasks, groups, cfg, name, sched, schedule, place, order, node_rank, programs, param_bytes,
+                    world, cap_gb, args=args, requests=requests, input_parts=input_parts)
+
+    p = place_under(caps_gb)
+    if kv_cache is not None:
+        over = _kv_over_cap(p, caps_gb)
+        if over and resume is None:
+            # A policy budgets parameters against the whole cap and sees a cache only while its
+            # attention task runs, but the caches persist: place once more with what this placement
+            # needs for caches and activations set aside on every GPU
+            reserve = [(kv + pr.act_arena_bytes) / 1e9 for kv, pr in zip(p.kv_cache_bytes, p.programs)]
+            if all(caps_gb[r] > reserve[r] for r in range(world)):
+                p = place_under([caps_gb[r] - reserve[r] for r in range(world)])
+                over = _kv_over_cap(p, caps_gb)
+        if over:
+            raise ValueError(over)
     p.stats = plan_stats(p)
     return p
+
+
+def _kv_over_cap(p: Plan, caps_gb: Sequence[float]) -> Optional[str]:
+    """Sets ``p.kv_cache_bytes`` (per rank: the caches of the attention tasks placed there) and
+    says which GPU, if any, cannot hold its parameter arena, activation arena and caches together:
+    caches persist across tasks, unlike activations."""
+    per_rank = [0] * p.world
+    for t in p.tasks:
+        if t.op is not None and t.op.kind == "attention" and t.id in p.placement:
+            per_rank[p.placement[t.id]] += registry.kv_cache_bytes(t.op)
+    p.kv_cache_bytes = per_rank
+    for r, pr in enumerate(p.programs):
+        cap = int(caps_gb[r] * 1e9)
+        if pr.param_arena_bytes + pr.act_arena_bytes + per_rank[r] > cap:
+            return (f"GPU {r}: parameter arena {pr.param_arena_bytes / 1e9:.6f} GB + activation arena "
+                    f"{pr.act_arena_bytes / 1e9:.6f} GB + KV caches {per_rank[r] / 1e9:.6f} GB exceed its cap of "
+                    f"{cap / 1e9:.6f} GB")
+    return None
 
 
 def real_time_s(t: Task, param_bytes: Dict[str, int]) -> float:
@@ -269,6 +333,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["weight_dtype"] = (saved.get("weight_dtype", "bf16"), args.get("weight_dtype", "bf16"))
     if saved.get("act_dtype", "bf16") != args.get("act_dtype", "bf16"):
         mismatch["act_dtype"] = (saved.get("act_dtype", "bf16"), args.get("act_dtype", "bf16"))
+    if saved.get("kv_cache") != args.get("kv_cache"):
+        mismatch["kv_cache"] = (saved.get("kv_cache"), args.get("kv_cache"))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -461,6 +527,7 @@ def plan_stats(p: Plan) -> Dict:
         "kernels_per_rank": [pr.n_kernels for pr in p.programs],
         "param_peak_gb_per_rank": [pr.param_peak_bytes / 1e9 for pr in p.programs],
         "act_arena_gb_per_rank": [pr.act_arena_bytes / 1e9 for pr in p.programs],
+        **({"kv_cache_gb_per_rank": [b / 1e9 for b in p.kv_cache_bytes]} if p.kv_cache_bytes else {}),
         # parameter bytes re-filled per steady-state step (evict/reload traffic of the plan)
         "refill_gb_per_step_per_rank": [steady_fill_bytes(pr, p.param_bytes) / 1e9 for pr in p.programs],
         # of which received from a peer GPU's arena over xGMI (RCCL p2p) instead of the host
