@@ -7,7 +7,10 @@ microsecond of event overhead) — for T new tokens per step from a context of P
 (executor.kv_randomize). The M = B*T <= 16 GEMMs run on the tiles the prefill shapes use: their
 share of the step is the baseline a GEMV path would be measured against.
 
-    python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--out FILE]
+    python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--kv-dtype fp8] [--only B,T,past]
+                                     [--out FILE]
+
+--kv-dtype fp8: the caches hold e4m3 bytes and per-(position, KV head) scales (runtime.plan kv_dtype).
 
 Needs a GPU.
 """
@@ -26,9 +29,9 @@ from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
 CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, past)
 
 
-def one(model, C, B, T, past, steps=10, rounds=5):
+def one(model, C, B, T, past, steps=10, rounds=5, kv_dtype="bf16"):
     dev = torch.device("cuda:0")
-    p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C)
+    p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype)
     ex = runtime.make_executor(p, 0, dev, runtime.make_store(p, device_init=runtime.device_init_ok(p, 0)))
     ex.kv_randomize(past)
     ex.step()
@@ -53,7 +56,7 @@ def one(model, C, B, T, past, steps=10, rounds=5):
     tl = ex.step(profile=True).timeline
     total = sum(t1 - t0 for _, t0, t1 in tl)
     kinds = {i.task: i.kind for i in p.programs[0].instrs if i.op == "run"}
-    lines = [f"{model}  B {B}  T {T}  past {past}  cache {C} ({sum(p.kv_cache_bytes) / 1e6:.1f} MB): "
+    lines = [f"{model}  B {B}  T {T}  past {past}  cache {C} ({kv_dtype}, {sum(p.kv_cache_bytes) / 1e6:.1f} MB): "
              f"{statistics.median(ms) * 1e3:.1f} us per step as one hipGraph of {ex.launches} kernel launches "
              f"(min {min(ms) * 1e3:.1f}, max {max(ms) * 1e3:.1f} over {rounds} rounds of {steps} steps)",
              f"  {'kernel group (eager, event pairs)':58s} {'us':>8s} {'share':>6s}"]
@@ -71,10 +74,10 @@ def one(model, C, B, T, past, steps=10, rounds=5):
     return lines
 
 
-def step_breakdown(model="llama3-8b-1l", C=8192):
+def step_breakdown(model="llama3-8b-1l", C=8192, kv_dtype="bf16", cases=CASES):
     out = []
-    for B, T, past in CASES:
-        out += one(model, C, B, T, past) + [""]
+    for B, T, past in cases:
+        out += one(model, C, B, T, past, kv_dtype=kv_dtype) + [""]
     return out
 
 
@@ -82,11 +85,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3-8b-1l")
     ap.add_argument("--kv-cache", type=int, default=8192)
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--only", default=None, help="B,T,past: one case")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("decode_step.py needs a GPU")
-    lines = step_breakdown(a.model, a.kv_cache)
+    cases = [tuple(int(x) for x in a.only.split(","))] if a.only else CASES
+    lines = step_breakdown(a.model, a.kv_cache, a.kv_dtype, cases)
     print("\n".join(lines), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

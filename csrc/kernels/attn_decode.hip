@@ -475,13 +475,18 @@ void attn_decode_sizes(const DecodeArgs& a, size_t* part_floats, size_t* counter
 }
 
 void launch_attn_decode(const DecodeArgs& a, hipStream_t s) {
+  if (a.kv_fp8) return launch_attn_decode_fp8(a, s);  // attn_decode_fp8.hip
   const int KC = chunk_of(a), ng = col_groups(a);
   if (a.D == 64) launch_decode_d<64>(a, ng, KC, s);
   else launch_decode_d<128>(a, ng, KC, s);
 }
 
 void launch_kv_append(const void* k_new, int ldk, const void* v_new, int ldv, void* k_cache, void* v_cache,
-                      const int* pos, int B, int T, int C, int row_elems, hipStream_t s) {
+                      float* k_scale, float* v_scale, const int* pos, int B, int T, int C, int row_elems,
+                      int n_kv_head, hipStream_t s) {
+  if (k_scale)  // e4m3 caches: attn_decode_fp8.hip
+    return launch_kv_append_fp8(k_new, ldk, v_new, ldv, k_cache, v_cache, k_scale, v_scale, pos, B, T, C, n_kv_head,
+                                row_elems / n_kv_head, s);
   const int total = B * T * 2 * (row_elems / 8);
   hipLaunchKernelGGL(kv_append_kernel, dim3((total + 255) / 256), dim3(256), 0, s, static_cast<const bf16*>(k_new),
                      ldk, static_cast<const bf16*>(v_new), ldv, static_cast<bf16*>(k_cache),

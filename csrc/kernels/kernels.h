@@ -295,12 +295,13 @@ struct AttnArgs {
 void launch_attention_fwd(const AttnArgs& a, hipStream_t s);
 void attention_split_sizes(const AttnArgs& a, size_t* part_floats, size_t* counters);
 
-// KV cache and decode steps (attn_decode.hip). The caches are bf16 [B][C][n_kv_head*D]; pos is
-// int32 [B] in device memory (the length of every sequence before the step), so one captured
-// launch serves every step.
+// KV cache and decode steps (attn_decode.hip, attn_decode_fp8.hip). The caches are bf16
+// [B][C][n_kv_head*D], or with kv_fp8 e4m3 bytes of that shape plus fp32 power-of-two scales
+// [B][n_kv_head][C], one per (position, KV head); pos is int32 [B] in device memory (the length of
+// every sequence before the step), so one captured launch serves every step.
 struct DecodeArgs {
   const void* q; int ldq;  // bf16 [B*T][>= n_head*D], row b*T + t, head h at column h*D
-  const void* k_cache;     // bf16 [B][C][n_kv_head*D]
+  const void* k_cache;     // bf16 [B][C][n_kv_head*D]; kv_fp8: e4m3 bytes
   const void* v_cache;
   void* o; int ldo;        // bf16 [B*T][>= n_head*D]
   const int* pos;          // int32 [B]: query t of sequence b sits at position pos[b] + t
@@ -309,6 +310,9 @@ struct DecodeArgs {
   int chunk = 0;           // keys per workgroup (a multiple of 64); 0: attn_decode_chunk()
   void* part = nullptr;    // fp32 partials, attn_decode_sizes() floats
   void* cnt = nullptr;     // int32 tickets, zero before the first launch (self-resetting)
+  bool kv_fp8 = false;     // e4m3 caches with the two scale tensors below
+  const float* k_scale = nullptr;  // fp32 [B][n_kv_head][C]
+  const float* v_scale = nullptr;
 };
 // T in 1..16, (n_head / n_kv_head) * T <= 64, D 64 or 128
 bool attn_decode_supported(int T, int n_head, int n_kv_head, int D);
@@ -316,10 +320,18 @@ bool attn_decode_supported(int T, int n_head, int n_kv_head, int D);
 int attn_decode_chunk(int B, int C, int n_kv_head, int D);
 void attn_decode_sizes(const DecodeArgs& a, size_t* part_floats, size_t* counters);
 void launch_attn_decode(const DecodeArgs& a, hipStream_t s);
+void launch_attn_decode_fp8(const DecodeArgs& a, hipStream_t s);  // what launch_attn_decode calls with kv_fp8
 // rows pos[b] .. pos[b]+T-1 of sequence b's caches = rows b*T .. b*T+T-1 of k_new / v_new
-// (bf16 [B*T][>= n_kv_head*D] views, 16-byte aligned rows); rows at or past C are dropped
+// (bf16 [B*T][>= n_kv_head*D] views, 16-byte aligned rows); rows at or past C are dropped.
+// With k_scale / v_scale (fp32 [B][n_kv_head][C]) the caches are e4m3 bytes: every head's D values
+// of a row are quantised by the rule of quantize_fp8 and the scale lands at [b][h][pos[b]+t]
+// (row_elems / n_kv_head a multiple of 8, at most 128).
 void launch_kv_append(const void* k_new, int ldk, const void* v_new, int ldv, void* k_cache, void* v_cache,
-                      const int* pos, int B, int T, int C, int row_elems, hipStream_t s);
+                      float* k_scale, float* v_scale, const int* pos, int B, int T, int C, int row_elems,
+                      int n_kv_head, hipStream_t s);
+void launch_kv_append_fp8(const void* k_new, int ldk, const void* v_new, int ldv, void* k_cache, void* v_cache,
+                          float* k_scale, float* v_scale, const int* pos, int B, int T, int C, int n_kv_head, int D,
+                          hipStream_t s);
 // tok_out[b*T + t] = tokens[b][p], out_i[b*T + t] = tab_i[p] (rows of row_bytes_i, a multiple of 16;
 // tab_i may be null) with p = min(pos[b] + t, C - 1)
 void launch_decode_prologue(const int* pos, const int* tokens, int* tok_out, const void* tab0, void* out0,

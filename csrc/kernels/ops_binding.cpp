@@ -603,22 +603,48 @@ void check_i32(const at::Tensor& t, int64_t n, const char* name) {
               " must be a contiguous int32 GPU tensor of ", n, " elements");
 }
 
-// caches [B][C][n_kv_head*D] bf16, contiguous
-void check_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t row_elems) {
+// caches [B][C][n_kv_head*D] contiguous: bf16, or with the two scale tensors e4m3 bytes (uint8)
+// and fp32 scales [B][n_kv_head][C]. Returns whether the caches are fp8.
+bool check_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t row_elems,
+                  const c10::optional<at::Tensor>& k_scale, const c10::optional<at::Tensor>& v_scale,
+                  int64_t n_kv_head) {
+  TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale go together");
+  const bool fp8 = k_cache.scalar_type() == at::kByte;
+  TORCH_CHECK(fp8 == k_scale.has_value(),
+              fp8 ? "uint8 (e4m3) caches need k_scale and v_scale" : "k_scale / v_scale go with uint8 (e4m3) caches");
   for (auto* p : {&k_cache, &v_cache}) {
-    check_bf16(*p, "cache");
+    if (fp8) {
+      TORCH_CHECK(p->is_cuda() && p->scalar_type() == at::kByte, "cache must be a uint8 GPU tensor");
+    } else {
+      check_bf16(*p, "cache");
+    }
     TORCH_CHECK(p->dim() == 3 && p->is_contiguous() && p->size(2) == row_elems &&
                     reinterpret_cast<uintptr_t>(p->data_ptr()) % 16 == 0,
                 "caches must be contiguous [B][C][n_kv_head*head_dim], 16-byte aligned");
   }
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes() && k_cache.size(1) >= 1, "k_cache and v_cache must match");
+  if (fp8) {
+    for (auto* p : {&*k_scale, &*v_scale})
+      TORCH_CHECK(p->is_cuda() && p->scalar_type() == at::kFloat && p->is_contiguous() && p->dim() == 3 &&
+                      p->size(0) == k_cache.size(0) && p->size(1) == n_kv_head && p->size(2) == k_cache.size(1) &&
+                      reinterpret_cast<uintptr_t>(p->data_ptr()) % 16 == 0,
+                  "scales must be contiguous fp32 GPU tensors [B][n_kv_head][C], 16-byte aligned");
+  }
+  return fp8;
 }
 
 void kv_append(const at::Tensor& k_new, const at::Tensor& v_new, const at::Tensor& k_cache,
-               const at::Tensor& v_cache, const at::Tensor& pos, int64_t T) {
+               const at::Tensor& v_cache, const at::Tensor& pos, int64_t T,
+               const c10::optional<at::Tensor>& k_scale, const c10::optional<at::Tensor>& v_scale) {
+  TORCH_CHECK(k_cache.dim() == 3, "caches must be [B][C][n_kv_head*head_dim]");
   const int64_t B = k_cache.size(0), C = k_cache.size(1), E = k_cache.size(2);
-  check_caches(k_cache, v_cache, E);
+  const int64_t n_kv_head = k_scale.has_value() && k_scale->dim() == 3 ? k_scale->size(1) : 1;
+  const bool fp8 = check_caches(k_cache, v_cache, E, k_scale, v_scale, n_kv_head);
   TORCH_CHECK(E % 8 == 0 && T >= 1, "kv_append: cache rows must be a multiple of 8 elements, T >= 1");
+  if (fp8) {
+    TORCH_CHECK(n_kv_head >= 1 && E % n_kv_head == 0 && E / n_kv_head % 8 == 0 && E / n_kv_head <= 128,
+                "kv_append: fp8 caches need head_dim a multiple of 8, at most 128");
+  }
   for (auto* p : {&k_new, &v_new}) {
     check_bf16(*p, "k/v");
     check_rows(*p, "k/v");
@@ -627,8 +653,9 @@ void kv_append(const at::Tensor& k_new, const at::Tensor& v_new, const at::Tenso
   check_i32(pos, B, "pos");
   TORCH_CHECK(B * T * E < (1ll << 30), "kv_append: step too large");
   launch_kv_append(k_new.data_ptr(), (int)k_new.stride(0), v_new.data_ptr(), (int)v_new.stride(0),
-                   k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(), (int)B, (int)T, (int)C, (int)E,
-                   cur_stream());
+                   k_cache.data_ptr(), v_cache.data_ptr(), fp8 ? k_scale->data_ptr<float>() : nullptr,
+                   fp8 ? v_scale->data_ptr<float>() : nullptr, pos.data_ptr<int>(), (int)B, (int)T, (int)C, (int)E,
+                   (int)n_kv_head, cur_stream());
 }
 
 DecodeArgs decode_args(int64_t B, int64_t T, int64_t C, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
@@ -656,11 +683,13 @@ std::tuple<int64_t, int64_t> attention_decode_sizes(int64_t B, int64_t T, int64_
 at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                             const at::Tensor& pos, int64_t T, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
                             double scale, const at::Tensor& part, const at::Tensor& cnt,
-                            const c10::optional<at::Tensor>& out, int64_t chunk) {
+                            const c10::optional<at::Tensor>& out, int64_t chunk,
+                            const c10::optional<at::Tensor>& k_scale, const c10::optional<at::Tensor>& v_scale) {
   TORCH_CHECK(k_cache.dim() == 3, "caches must be [B][C][n_kv_head*head_dim]");
   const int64_t B = k_cache.size(0), C = k_cache.size(1);
   DecodeArgs a = decode_args(B, T, C, n_head, n_kv_head, head_dim, chunk);
-  check_caches(k_cache, v_cache, n_kv_head * head_dim);
+  a.kv_fp8 = check_caches(k_cache, v_cache, n_kv_head * head_dim, k_scale, v_scale, n_kv_head);
+  if (a.kv_fp8) a.k_scale = k_scale->data_ptr<float>(), a.v_scale = v_scale->data_ptr<float>();
   check_bf16(q, "q");
   check_rows(q, "q");
   TORCH_CHECK(q.size(0) == B * T && q.size(1) >= n_head * head_dim, "q must be [B*T][>= n_head*head_dim]");
@@ -1565,7 +1594,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = 0.125, py::arg("out") = py::none(), py::arg("variant") = 0, py::arg("Sq") = 0,
         py::arg("q_off") = 0, py::arg("flags") = 0);
   m.def("kv_append", &kv_append, py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("pos"), py::arg("T"));
+        py::arg("pos"), py::arg("T"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("attention_decode_sizes", &attention_decode_sizes, py::arg("B"), py::arg("T"), py::arg("C"),
         py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("chunk") = 0);
   m.def("attention_decode_chunk", [](int64_t B, int64_t C, int64_t n_kv_head, int64_t head_dim) {
@@ -1573,7 +1602,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("attention_decode", &attention_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("pos"),
         py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("scale"),
-        py::arg("part"), py::arg("cnt"), py::arg("out") = py::none(), py::arg("chunk") = 0);
+        py::arg("part"), py::arg("cnt"), py::arg("out") = py::none(), py::arg("chunk") = 0,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("decode_prologue", &decode_prologue, py::arg("pos"), py::arg("tokens"), py::arg("tok_out"), py::arg("T"),
         py::arg("C"), py::arg("tables"), py::arg("outs"));
   m.def("norm", &norm, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5,

@@ -25,7 +25,8 @@ only; mxfp4 = OCP MXFP4, e2m1 + one e8m0 scale per 32 elements, dense models, ne
 mxfp4-experts = MXFP4 for the expert weights of an MoE model only, needs --act-dtype fp8),
 --act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8, mxfp4 or mxfp4-experts: GEMM inputs quantised per row,
 multiplied on the block-scaled MFMA against the fp8 or fp4 weight), --kv-cache C (decode steps: --seq is
-the number of new tokens per step and every attention node keeps a KV cache of C positions) and, for
+the number of new tokens per step and every attention node keeps a KV cache of C positions),
+--kv-dtype {bf16,fp8} (with --kv-cache: fp8 = e4m3 cache bytes + one fp32 scale per position and KV head) and, for
 ``run``, --past P (the caches are filled with random rows to length P before the timed steps).
 """
 from __future__ import annotations
@@ -73,6 +74,9 @@ def _common(ap: argparse.ArgumentParser) -> None:
                     help="decode steps: --seq becomes the number of new tokens per step (1 .. 16) and every attention "
                          "node keeps K/V caches of C positions per sequence on its GPU; the caches count against "
                          "--hbm-cap-gb (dense gpt2 / llama models; no --tp / --sp)")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="with --kv-cache: how the caches are stored: bf16, or fp8 (OCP e4m3 + one fp32 power-of-two "
+                         "scale per position and KV head: (head_dim + 4) / (2 head_dim) of the bf16 bytes)")
     ap.add_argument("--past", type=int, default=0, metavar="P",
                     help="run, with --kv-cache: every sequence starts from a context of P positions of random cache "
                          "rows (the timed steps then run at that length without P / seq steps before them)")
@@ -85,7 +89,8 @@ def _plan(a, world: int, resume: Optional[str] = None):
     return runtime.plan(a.model, world=world, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, replicas=a.replicas,
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
                         placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
-                        act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None))
+                        act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None),
+                        kv_dtype=getattr(a, "kv_dtype", "bf16"))
 
 
 def _has_kv(p) -> bool:
@@ -97,7 +102,8 @@ def _kv_fields(a, p) -> dict:
     """JSON fields of a plan with KV caches: the capacity, the context the run starts from, the cache bytes."""
     if not _has_kv(p):
         return {}
-    return {"kv_cache": a.kv_cache, "past": a.past, "kv_cache_gb": sum(p.kv_cache_bytes) / 1e9}
+    return {"kv_cache": a.kv_cache, "past": a.past, "kv_cache_gb": sum(p.kv_cache_bytes) / 1e9,
+            "kv_dtype": p.args.get("kv_dtype", "bf16")}
 
 
 def _kv_check(a, n_steps: int, what: str) -> None:

@@ -36,6 +36,19 @@ def _a8(act_dtype: str) -> bool:
     return act_dtype == "fp8"
 
 
+def _kv8(kv_dtype: str) -> bool:
+    if kv_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+    return kv_dtype == "fp8"
+
+
+def _qdq_heads(x: torch.Tensor, D: int) -> torch.Tensor:
+    """K or V rows [B, S, n_kv_head*D] through the e4m3 quantise-dequantise of an fp8 KV cache:
+    one power-of-two scale per (position, KV head)."""
+    q, s = quantize_fp8(x.reshape(-1, D))
+    return dequantize_fp8(q, s, torch.float32).reshape(x.shape)
+
+
 def _attn(q, k, v, nh, nkv, D, causal=True):
     B, S = q.shape[0], q.shape[1]
     q = q.view(B, S, nh, D).transpose(1, 2)
@@ -52,10 +65,10 @@ def _attn(q, k, v, nh, nkv, D, causal=True):
 
 @torch.no_grad()
 def gpt2_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, hidden: list = None,
-                 act_dtype: str = "bf16") -> torch.Tensor:
+                 act_dtype: str = "bf16", kv_dtype: str = "bf16") -> torch.Tensor:
     """tokens [B, S] -> logits [B, S, V] (fp32). ``hidden`` (if a list) receives the residual
-    stream after every block. ``act_dtype``: see :func:`forward`."""
-    a8 = _a8(act_dtype)
+    stream after every block. ``act_dtype``, ``kv_dtype``: see :func:`forward`."""
+    a8, kv8 = _a8(act_dtype), _kv8(kv_dtype)
     B, S = tokens.shape
     H, nh = cfg.n_embd, cfg.n_head
     x = _w(store, "wte")[tokens.long()] + _w(store, "wpe")[:S][None]
@@ -63,7 +76,10 @@ def gpt2_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, hidd
         p = f"h.{i}."
         h = F.layer_norm(x, (H,), _w(store, p + "ln_1.weight"), _w(store, p + "ln_1.bias"), cfg.norm_eps)
         qkv = _mm(store, h, p + "attn.c_attn.weight", a8) + _w(store, p + "attn.c_attn.bias")
-        a = _attn(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], nh, nh, cfg.head_dim)
+        k, v = qkv[..., H:2 * H], qkv[..., 2 * H:]
+        if kv8:
+            k, v = _qdq_heads(k, cfg.head_dim), _qdq_heads(v, cfg.head_dim)
+        a = _attn(qkv[..., :H], k, v, nh, nh, cfg.head_dim)
         x = x + _mm(store, a, p + "attn.c_proj.weight", a8) + _w(store, p + "attn.c_proj.bias")
         h = F.layer_norm(x, (H,), _w(store, p + "ln_2.weight"), _w(store, p + "ln_2.bias"), cfg.norm_eps)
         h = F.gelu(_mm(store, h, p + "mlp.c_fc.weight", a8) + _w(store, p + "mlp.c_fc.bias"), approximate="tanh")
@@ -91,12 +107,12 @@ def _rms(x, w, eps):
 
 @torch.no_grad()
 def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None,
-                  act_dtype: str = "bf16") -> torch.Tensor:
+                  act_dtype: str = "bf16", kv_dtype: str = "bf16") -> torch.Tensor:
     """Llama-3 / Mixtral forward (fp32): tokens [B, S] -> logits [B, S, V]. ``router_margins``
     (if a list) receives, per MoE layer, the [B, S] gap between the k-th and (k+1)-th router
     logit: tokens with a tiny gap may legitimately route differently under bf16 logits.
-    ``act_dtype``: see :func:`forward`."""
-    a8 = _a8(act_dtype)
+    ``act_dtype``, ``kv_dtype``: see :func:`forward`."""
+    a8, kv8 = _a8(act_dtype), _kv8(kv_dtype)
     B, S = tokens.shape
     nh, nkv, D = cfg.n_head, cfg.kv_heads, cfg.head_dim
     x = _w(store, "tok_embeddings")[tokens.long()]
@@ -106,6 +122,8 @@ def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, rou
         qkv = _mm(store, h, p + "attention.wqkv", a8)
         q, k, v = qkv[..., :nh * D], qkv[..., nh * D:(nh + nkv) * D], qkv[..., (nh + nkv) * D:]
         q, k = _rope(q, S, D, cfg.rope_theta), _rope(k, S, D, cfg.rope_theta)
+        if kv8:
+            k, v = _qdq_heads(k, D), _qdq_heads(v, D)
         x = x + _mm(store, _attn(q, k, v, nh, nkv, D), p + "attention.wo", a8)
         h = _rms(x, _w(store, p + "ffn_norm.weight"), cfg.norm_eps)
         if cfg.n_experts:
@@ -131,12 +149,13 @@ def llama_forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, rou
 
 
 def forward(cfg: ModelConfig, store: ParamStore, tokens: torch.Tensor, router_margins: list = None,
-            act_dtype: str = "bf16") -> torch.Tensor:
+            act_dtype: str = "bf16", kv_dtype: str = "bf16") -> torch.Tensor:
     """``act_dtype="fp8"``: the input of every GEMM whose weight the store holds quantised is
     quantise-dequantised per row (``quantize_fp8`` / ``dequantize_fp8``: e4m3, one power-of-two
     scale per row) — what the executor's fp8-activation mode multiplies, over fp8 and mxfp4
-    weights alike (``store.tensor`` is the dequantised weight in either format). The default changes
-    nothing."""
+    weights alike (``store.tensor`` is the dequantised weight in either format). ``kv_dtype="fp8"``:
+    K (after RoPE) and V are quantise-dequantised per (position, KV head) before attention — what
+    an fp8 KV cache holds. The defaults change nothing."""
     if cfg.family == "gpt2":
-        return gpt2_forward(cfg, store, tokens, act_dtype=act_dtype)
-    return llama_forward(cfg, store, tokens, router_margins, act_dtype=act_dtype)
+        return gpt2_forward(cfg, store, tokens, act_dtype=act_dtype, kv_dtype=kv_dtype)
+    return llama_forward(cfg, store, tokens, router_margins, act_dtype=act_dtype, kv_dtype=kv_dtype)

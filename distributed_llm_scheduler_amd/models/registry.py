@@ -118,14 +118,30 @@ def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: i
                          f"kernel's {KV_MAX_COLS} query rows per KV head")
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
+def check_kv_dtype(kv_dtype: str, kv_cache: "int | None") -> None:
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+    if kv_dtype != "bf16" and kv_cache is None:
+        raise ValueError(f"kv_dtype={kv_dtype!r} needs a KV cache (kv_cache=C)")
+
+
 def kv_cache_bytes(op, dtype_bytes: int = 2) -> int:
-    """Bytes of an attention node's K and V caches: 2 * B * C * n_kv_head * head_dim * dtype_bytes."""
+    """Bytes of an attention node's K and V caches: 2 * B * C * n_kv_head * head_dim * dtype_bytes;
+    with ``attrs["kv_dtype"] == "fp8"`` 2 * B * C * n_kv_head * (head_dim + 4): one e4m3 byte per
+    element and one fp32 scale per (position, KV head)."""
     a = op.attrs
+    if a.get("kv_dtype", "bf16") == "fp8":
+        return 2 * op.out_shape[0] * a["kv_cache"] * a["n_kv_head"] * (a["head_dim"] + 4)
     return 2 * op.out_shape[0] * a["kv_cache"] * a["n_kv_head"] * a["head_dim"] * dtype_bytes
 
 
-def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_model: str = "bytes") -> None:
-    """In place: every attention node carries ``attrs["kv_cache"] = C``; its ``memory_required``
+def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_model: str = "bytes",
+                 kv_dtype: str = "bf16") -> None:
+    """In place: every attention node carries ``attrs["kv_cache"] = C`` (and ``attrs["kv_dtype"]``
+    when that is not bf16); its ``memory_required``
     grows by its cache bytes (which persist across steps, unlike its activations, so every policy
     sees what the node needs on its GPU); its flops count the score terms over the cache length
     (T queries x C keys in place of the causal T x T), and under the ``bytes`` cost model its time
@@ -136,6 +152,8 @@ def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_mo
         if t.op is None or t.op.kind != "attention":
             continue
         t.op.attrs["kv_cache"] = int(kv_cache)
+        if kv_dtype != "bf16":
+            t.op.attrs["kv_dtype"] = kv_dtype
         a = t.op.attrs
         cache = kv_cache_bytes(t.op)
         core_old = 2.0 * batch * a["n_head"] * seq * seq * a["head_dim"]
@@ -151,7 +169,8 @@ def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_mo
 
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
           tp: int = 1, sp: int = 1, weight_dtype: str = "bf16", act_dtype: str = "bf16",
-          kv_cache: "int | None" = None) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          kv_cache: "int | None" = None,
+          kv_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
@@ -167,7 +186,10 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     tensors ``"fp8-experts"`` marks, stored as MXFP4 — router, attention and LM head stay bf16; not
     with a model without experts, ``tp`` or ``sp``; every marked K a multiple of 32, and
     ``act_dtype="fp8"`` (the grouped kernel is W4A8). ``kv_cache=C``: ``seq`` is the number of new
-    tokens per step and every attention node keeps a KV cache of C positions (:func:`add_kv_cache`)."""
+    tokens per step and every attention node keeps a KV cache of C positions (:func:`add_kv_cache`).
+    ``kv_dtype="fp8"`` (needs ``kv_cache``; independent of ``weight_dtype`` / ``act_dtype``): the
+    caches hold e4m3 bytes and one fp32 scale per (position, KV head) (:func:`kv_cache_bytes`)."""
+    check_kv_dtype(kv_dtype, kv_cache)
     known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
     if weight_dtype not in known:
         raise ValueError(f"weight_dtype must be one of {known}, got {weight_dtype!r}")
@@ -204,7 +226,7 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
     if kv_cache is not None:
-        add_kv_cache(tasks, batch, seq, kv_cache, cost_model)
+        add_kv_cache(tasks, batch, seq, kv_cache, cost_model, kv_dtype)
     groups = param_groups(cfg)
     if tp > 1:
         from .transforms import tensor_parallel

@@ -701,21 +701,62 @@ def attention(q, k, v, B, S, n_head, n_kv_head, head_dim, causal=True, scale=Non
 # ---------------------------------------------------------- KV cache and decode steps
 # Caches are bf16 [B][C][n_kv_head*head_dim]; ``pos`` (int32 [B], on the caches' device) holds
 # every sequence's length before the step, so a captured step follows a growing sequence.
+# fp8 caches (``k_scale`` / ``v_scale`` given): uint8 e4m3 bytes of the same shape plus fp32
+# power-of-two scales [B][n_kv_head][C], one per (position, KV head) by the rule of quantize_fp8.
 
 DECODE_HEAD_DIMS = (64, 128)  # head_dim instances of the GPU decode attention kernel (the CPU path takes any)
 
-def kv_append(k_new, v_new, k_cache, v_cache, pos, T):
+
+def _kv_scales_ok(k_cache, v_cache, k_scale, v_scale, what):
+    """Whether the caches are fp8; the checks the GPU binding makes, for the CPU path."""
+    if (k_scale is None) != (v_scale is None):
+        raise RuntimeError(f"{what}: k_scale and v_scale go together")
+    fp8 = k_cache.dtype == torch.uint8
+    if fp8 != (k_scale is not None):
+        raise RuntimeError(f"{what}: uint8 (e4m3) caches need k_scale and v_scale" if fp8 else
+                           f"{what}: k_scale / v_scale go with uint8 (e4m3) caches")
+    if fp8:
+        B, C, E = k_cache.shape
+        for s_ in (k_scale, v_scale):
+            if s_.dtype != torch.float32 or s_.dim() != 3 or s_.shape[0] != B or s_.shape[2] != C \
+                    or s_.shape[1] < 1 or E % s_.shape[1] or s_.shape != k_scale.shape:
+                raise RuntimeError(f"{what}: scales must be fp32 [B][n_kv_head][C]")
+    return fp8
+
+
+def kv_dequantize(cache, scale):
+    """An fp8 cache (uint8 e4m3 [B][C][E]) and its scales (fp32 [B][n_kv_head][C]) as bf16
+    [B][C][E]: exact, every e4m3 value times a power of two being a bf16 value."""
+    B, C, E = cache.shape
+    H = scale.shape[1]
+    x = cache.view(torch.float8_e4m3fn).float().view(B, C, H, E // H)
+    return (x * scale.transpose(1, 2)[..., None]).to(torch.bfloat16).view(B, C, E)
+
+
+def kv_append(k_new, v_new, k_cache, v_cache, pos, T, k_scale=None, v_scale=None):
     """Rows ``pos[b] .. pos[b]+T-1`` of sequence b's caches <- rows ``b*T .. b*T+T-1`` of
     ``k_new`` / ``v_new`` ([B*T][>= n_kv_head*head_dim], column views of the packed qkv buffer
-    allowed). Rows at or past the capacity C are dropped."""
+    allowed). Rows at or past the capacity C are dropped. With ``k_scale`` / ``v_scale`` the caches
+    are fp8: every head's row is quantised by :func:`quantize_fp8` and its scale lands at
+    ``[b][h][pos[b]+t]`` (GPU: attn_decode_fp8.hip)."""
     if _gpu(k_cache):
-        ext().kv_append(k_new, v_new, k_cache, v_cache, pos, int(T))
+        ext().kv_append(k_new, v_new, k_cache, v_cache, pos, int(T), k_scale, v_scale)
         return
+    fp8 = _kv_scales_ok(k_cache, v_cache, k_scale, v_scale, "kv_append")
     B, C, E = k_cache.shape
     for b, p in enumerate(pos.tolist()):
         n = max(0, min(T, C - p))
-        k_cache[b, p:p + n] = k_new[b * T:b * T + n, :E]
-        v_cache[b, p:p + n] = v_new[b * T:b * T + n, :E]
+        if not fp8:
+            k_cache[b, p:p + n] = k_new[b * T:b * T + n, :E]
+            v_cache[b, p:p + n] = v_new[b * T:b * T + n, :E]
+            continue
+        if n == 0:
+            continue
+        H = k_scale.shape[1]
+        for new, cache, sc in ((k_new, k_cache, k_scale), (v_new, v_cache, v_scale)):
+            q, s_ = quantize_fp8(new[b * T:b * T + n, :E].to(torch.bfloat16).reshape(n * H, E // H))
+            cache[b, p:p + n] = q.view(torch.uint8).view(n, E)
+            sc[b, :, p:p + n] = s_.view(n, H).t()
 
 
 def attention_decode_sizes(B, T, C, n_head, n_kv_head, head_dim, chunk=0):
@@ -746,17 +787,23 @@ def ref_attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_di
 
 
 def attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None, out=None,
-                     workspace=None, chunk=0):
+                     workspace=None, chunk=0, k_scale=None, v_scale=None):
     """Causal attention of the T new queries of every sequence (q [B*T][>= n_head*head_dim])
     against its cache rows ``0 .. pos[b]+t``; runs after ``kv_append``. GPU: attn_decode.hip with
     ``workspace`` from ``attention_decode_workspace`` (``chunk``: keys per workgroup, 0 = the
-    launcher's choice; the workspace must be sized with the same value). CPU: fp32 torch."""
+    launcher's choice; the workspace must be sized with the same value). CPU: fp32 torch. With
+    ``k_scale`` / ``v_scale`` the caches are fp8 (attn_decode_fp8.hip; the workspace is the same);
+    the CPU path dequantises them first."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     if _gpu(q):
         if workspace is None:
             raise ValueError("attention_decode needs the workspace of attention_decode_workspace on the GPU")
         return ext().attention_decode(q, k_cache, v_cache, pos, int(T), n_head, n_kv_head, head_dim, float(scale),
-                                      workspace[0], workspace[1], out, int(chunk))
+                                      workspace[0], workspace[1], out, int(chunk), k_scale, v_scale)
+    if _kv_scales_ok(k_cache, v_cache, k_scale, v_scale, "attention_decode"):
+        if k_scale.shape[1] != n_kv_head:
+            raise RuntimeError("attention_decode: scales must be fp32 [B][n_kv_head][C]")
+        k_cache, v_cache = kv_dequantize(k_cache, k_scale), kv_dequantize(v_cache, v_scale)
     if not (1 <= T <= 16 and n_head % n_kv_head == 0 and n_head // n_kv_head * T <= 64):  # (any head_dim here)
         raise RuntimeError("attention_decode: needs 1 <= T <= 16 and (n_head / n_kv_head) * T <= 64 "
                            f"(T {T}, heads {n_head}/{n_kv_head})")

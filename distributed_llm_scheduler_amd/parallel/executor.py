@@ -1630,14 +1630,16 @@ class DAGExecutor:
                 # decode step: QKV of the T new tokens (RoPE from the table rows gathered at pos:
                 # with S = M the kernels' row % S is the row), append, attend the caches, project
                 st = self._kv[_kv_prefix(head.id)]
-                kc, vc = self._kv_cache[head.id]
+                kc, vc, *sc = self._kv_cache[head.id]
+                ks, vs = sc if sc else (None, None)  # kv_dtype="fp8": the scales of the byte caches
                 if a.get("rope"):
                     self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv,
                                rope=(st["cos_g"], st["sin_g"], M, D, (nh + nkv) * D), rope_perm=(nh, nkv, D))
                 else:
                     self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv)
-                ops.kv_append(qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], kc, vc, st["pos"], S)
-                ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, workspace=self._kv_ws)
+                ops.kv_append(qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], kc, vc, st["pos"], S, ks, vs)
+                ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, workspace=self._kv_ws,
+                                     k_scale=ks, v_scale=vs)
                 self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
                              post_norm=self._post_norm_out(self._flat(out)))
                 return
@@ -2723,7 +2725,7 @@ class DAGExecutor:
         m = {"activations": self.act_slab.numel(), "params": self.param_slab.numel(),
              "workspace": self.ws_slab.numel()}
         if self._kv_full is not None:
-            m["kv_cache"] = sum(k.numel() * 4 for k, _ in self._kv_cache.values())  # K and V, bf16
+            m["kv_cache"] = sum(c.numel() * c.element_size() for cs in self._kv_cache.values() for c in cs)
             m["kv_slab"] = self.kv_slab.numel()
         return m
 
@@ -2733,15 +2735,16 @@ class DAGExecutor:
         parameter and workspace slabs holds, for the requests this rank runs tasks of, ``pos``
         (int32 [B], each sequence's length, advanced on the device), the token stream [B][C] where
         the rank embeds, the step's gathered tokens / wpe / RoPE rows, the decode workspace, and
-        the K and V caches [B][C][n_kv_head*D] of the attention tasks it runs — all allocated
-        here, nothing during a step or a capture.
+        the K and V caches [B][C][n_kv_head*D] of the attention tasks it runs (``kv_dtype="fp8"``:
+        uint8 e4m3 bytes and fp32 scales [B][n_kv_head][C]) — all allocated here, nothing during a
+        step or a capture.
 
         Whether the plan has a cache is read from the whole DAG, and every rank keeps the host
         lengths of every request, also a rank that runs no embedding or attention task and so
         holds no device state: the KV interface works on all ranks alike, and a step past the
         capacity raises on all of them, not on some while the others wait for their edges."""
         self._kv: Dict[str, dict] = {}
-        self._kv_cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._kv_cache: Dict[str, Tuple[torch.Tensor, ...]] = {}  # (k, v), fp8: (k, v, k_scale, v_scale)
         self._kv_first: Dict[int, list] = {}  # index in prog.instrs -> states whose prologue runs before it
         self._kv_last: Dict[int, list] = {}  # ... -> states whose pos advances after it
         self._kv_full = self.kv_slab = self._kv_ws = None
@@ -2801,8 +2804,14 @@ class DAGExecutor:
                         st["cos"], st["sin"] = self._rope_tables(C, D, a.get("rope_theta", 10000.0))
                         want(pre, "cos_g", (B * T, D // 2), torch.float32)
                         want(pre, "sin_g", (B * T, D // 2), torch.float32)
-                    want(tid, "k", (B, C, nkv * D), self.dtype)
-                    want(tid, "v", (B, C, nkv * D), self.dtype)
+                    if a.get("kv_dtype", "bf16") == "fp8":
+                        want(tid, "k", (B, C, nkv * D), torch.uint8)
+                        want(tid, "v", (B, C, nkv * D), torch.uint8)
+                        want(tid, "ks", (B, nkv, C), torch.float32)
+                        want(tid, "vs", (B, nkv, C), torch.float32)
+                    else:
+                        want(tid, "k", (B, C, nkv * D), self.dtype)
+                        want(tid, "v", (B, C, nkv * D), self.dtype)
                     if self.gpu:
                         pf, nc = ops.attention_decode_sizes(B, T, C, nh, nkv, D)
                         ws_need = [max(ws_need[0], pf), max(ws_need[1], nc)]
@@ -2826,11 +2835,14 @@ class DAGExecutor:
             off += al(nbytes)
             if key == "@ws":
                 ws[fld] = v
-            elif fld in ("k", "v"):
+            elif fld in ("k", "v", "ks", "vs"):
                 caches.setdefault(key, {})[fld] = v
             else:
                 self._kv[key][fld] = v
-        self._kv_cache = {tid: (c["k"], c["v"]) for tid, c in caches.items()}
+        self._kv_cache = {tid: tuple(c[f] for f in ("k", "v", "ks", "vs") if f in c) for tid, c in caches.items()}
+        for cs in self._kv_cache.values():
+            for sc in cs[2:]:
+                sc.fill_(1.0)  # the scale of an all-zero row: a cache nobody wrote dequantises to zeros
         self._kv_ws = (ws["part"], ws["cnt"]) if ws else None
         vocab = self.cfg.vocab_size if self.cfg is not None else 50257
         for st in self._kv.values():
@@ -2901,11 +2913,22 @@ class DAGExecutor:
                 st["tokens"].copy_(t)
 
     def kv_randomize(self, lengths, seed: int = 0) -> None:
-        """Fill the caches with seeded bf16 N(0,1) rows and set the lengths: a context of P tokens
-        without P/T steps (benchmarks; weights and tokens are synthetic anyway)."""
+        """Fill the caches with seeded bf16 N(0,1) rows (fp8 caches: those rows quantised per
+        position and KV head) and set the lengths: a context of P tokens without P/T steps
+        (benchmarks; weights and tokens are synthetic anyway)."""
         self._kv_need()
         for tid in sorted(self._kv_cache):
             g = torch.Generator(device=self.device).manual_seed((zlib.crc32(tid.encode()) ^ seed) & 0x7FFFFFFF)
-            for c in self._kv_cache[tid]:
-                c.normal_(generator=g)
+            cs = self._kv_cache[tid]
+            for i, c in enumerate(cs[:2]):
+                if len(cs) == 2:
+                    c.normal_(generator=g)
+                    continue
+                B, C, E = c.shape
+                H = cs[2 + i].shape[1]
+                for b in range(B):  # a sequence at a time: the fp32 temporaries stay small
+                    rows = torch.empty(C * H, E // H, dtype=self.dtype, device=self.device).normal_(generator=g)
+                    q, sc = ops.quantize_fp8(rows)
+                    c[b].copy_(q.view(torch.uint8).view(C, E))
+                    cs[2 + i][b].copy_(sc.view(C, H).t())
         self.kv_reset(lengths)

@@ -70,7 +70,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          node_speeds: Optional[Sequence[float]] = None, link_bw_gbps: float = 153.0,
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
-         act_dtype: str = "bf16", kv_cache: Optional[int] = None) -> Plan:
+         act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16") -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -140,6 +140,13 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     C above the model's positions, T above 16, ``(n_head / n_kv_head) * T`` above 64, and with
     ``DLS_ATTN_BLOCK=1`` (the one-launch attention block has no cache).
 
+    ``kv_dtype="fp8"`` (with ``kv_cache`` only, independent of ``weight_dtype`` / ``act_dtype``;
+    anything else but ``"bf16"`` raises ``ValueError``): the caches hold e4m3 bytes and one fp32
+    power-of-two scale per (position, KV head), ``2 * batch * C * n_kv_head * (head_dim + 4)`` bytes
+    per attention node — what ``memory_required``, the cap check, its second placement and
+    ``Plan.kv_cache_bytes`` then count. The step appends quantised rows and attends on the bytes
+    (attn_decode_fp8.hip).
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -168,6 +175,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                              "has no KV cache")
         if placement not in ("scheduler", "replica", "pipeline"):
             raise ValueError(f"kv_cache: placement must be 'scheduler', 'replica' or 'pipeline', got {placement!r}")
+    registry.check_kv_dtype(kv_dtype, kv_cache)
+    if kv_dtype != "bf16":  # (only when not the default, as kv_cache)
+        args["kv_dtype"] = kv_dtype
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -182,7 +192,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
             for j, k in enumerate(members):
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
-                                        sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache)
+                                        sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache,
+                                        kv_dtype=kv_dtype)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
 
     def place_under(caps_now: Sequence[float]) -> Plan:
@@ -335,6 +346,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["act_dtype"] = (saved.get("act_dtype", "bf16"), args.get("act_dtype", "bf16"))
     if saved.get("kv_cache") != args.get("kv_cache"):
         mismatch["kv_cache"] = (saved.get("kv_cache"), args.get("kv_cache"))
+    if saved.get("kv_dtype", "bf16") != args.get("kv_dtype", "bf16"):
+        mismatch["kv_dtype"] = (saved.get("kv_dtype", "bf16"), args.get("kv_dtype", "bf16"))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
