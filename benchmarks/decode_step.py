@@ -8,9 +8,12 @@ microsecond of event overhead) — for T new tokens per step from a context of P
 share of the step is the baseline a GEMV path would be measured against.
 
     python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--kv-dtype fp8] [--only B,T,past]
-                                     [--out FILE]
+                                     [--out FILE] [--generate]
 
 --kv-dtype fp8: the caches hold e4m3 bytes and per-(position, KV head) scales (runtime.plan kv_dtype).
+--generate: instead of the breakdown, the T = 1 cases with and without on-device sampling
+(runtime.plan generate=True; temperature 0.8, top_k 50, top_p 0.9, and greedy) in one session, the
+captured steps alternating, and the difference.
 
 Needs a GPU.
 """
@@ -74,6 +77,49 @@ def one(model, C, B, T, past, steps=10, rounds=5, kv_dtype="bf16"):
     return lines
 
 
+def generate_delta(model, C, B, past, kv_dtype="bf16", steps=10, rounds=5):
+    """us per captured step without sampling, with greedy sampling and with (0.8, 50, 0.9), alternating."""
+    dev = torch.device("cuda:0")
+    exs = {}
+    for what, gen in (("plain", False), ("generate", True)):
+        p = runtime.plan(model, world=1, seq=1, batch=B, kv_cache=C, kv_dtype=kv_dtype, generate=gen)
+        ex = runtime.make_executor(p, 0, dev, runtime.make_store(p, device_init=runtime.device_init_ok(p, 0)))
+        ex.kv_randomize(past)
+        ex.step()
+        ex.kv_reset(past)
+        if not ex.capture():
+            raise RuntimeError("the decode step was not captured")
+        exs[what] = ex
+    assert past + steps <= C
+
+    def timed(ex):
+        ex.kv_reset(past)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            ex.step()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / steps * 1e3
+
+    t = {"plain": [], "greedy": [], "sampled": []}
+    for _ in range(rounds):
+        t["plain"].append(timed(exs["plain"]))
+        exs["generate"].set_sampling()
+        t["greedy"].append(timed(exs["generate"]))
+        exs["generate"].set_sampling(temperature=0.8, top_k=50, top_p=0.9, seed=1)
+        t["sampled"].append(timed(exs["generate"]))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    line = (f"{model}  B {B}  T 1  past {past}  cache {C} ({kv_dtype}): {med['plain']:.1f} us per step without sampling "
+            f"({exs['plain'].launches} launches), {med['greedy']:.1f} us greedy ({med['greedy'] - med['plain']:+.1f}), "
+            f"{med['sampled']:.1f} us at (0.8, 50, 0.9) ({med['sampled'] - med['plain']:+.1f}; "
+            f"{exs['generate'].launches} launches); medians of {rounds} alternating rounds of {steps} steps")
+    del exs
+    torch.cuda.empty_cache()
+    return [line]
+
+
 def step_breakdown(model="llama3-8b-1l", C=8192, kv_dtype="bf16", cases=CASES):
     out = []
     for B, T, past in cases:
@@ -88,11 +134,19 @@ def main():
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--only", default=None, help="B,T,past: one case")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--generate", action="store_true",
+                    help="the T = 1 cases with and without on-device sampling, alternating, and the difference")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("decode_step.py needs a GPU")
     cases = [tuple(int(x) for x in a.only.split(","))] if a.only else CASES
-    lines = step_breakdown(a.model, a.kv_cache, a.kv_dtype, cases)
+    if a.generate:
+        lines = []
+        for B, T, past in cases:
+            if T == 1:
+                lines += generate_delta(a.model, a.kv_cache, B, past, a.kv_dtype)
+    else:
+        lines = step_breakdown(a.model, a.kv_cache, a.kv_dtype, cases)
     print("\n".join(lines), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -338,6 +338,34 @@ void launch_decode_prologue(const int* pos, const int* tokens, int* tok_out, con
                             int row_bytes0, const void* tab1, void* out1, int row_bytes1, int B, int T, int C,
                             hipStream_t s);
 
+// Token sampling over the last logits row of every sequence (sample.hip): greedy, temperature,
+// top-k and top-p by whole value classes, a Philox4x32-10 draw in index order, and the stream
+// rule that feeds the token back into tokens[b][pos[b]+T]. One launch; a row is split over
+// `slices` workgroups whose partials the last arriver merges.
+struct SampleArgs {
+  const void* logits; int ld;  // bf16 [B*T][ld]; row b*T + T-1 is read, V valid columns
+  int V, B, T, C;
+  const int* pos;              // [B] sequence lengths before the step (never written)
+  int* tokens;                 // [B][C] token stream
+  const float* temperature;    // [B], 0 = greedy
+  const int* top_k;            // [B], 0 = off
+  const float* top_p;          // [B], >= 1 = off
+  const long long* seed;       // [1]
+  int request;                 // replica ordinal: Philox counter word 2
+  const int* prompt_len;       // [B] or null (0)
+  const int* eos;              // [1] or null (-1)
+  int* done;                   // [B] or null
+  int* next_out;               // [B]
+  float* stats;                // [B][4]: theta, Z, cumulative weight before the token, its weight
+  unsigned* part;              // sample_sizes() words, written and read inside the launch
+  int* cnt;                    // [B] tickets: zero before the first launch, reset by the launch
+};
+constexpr int kSampleMaxV = 1 << 20;
+// workgroups per row and elements per workgroup (a multiple of 8) for B rows of V logits
+void sample_slices(int B, int V, int* slices, int* slice_len);
+void sample_sizes(int B, int V, size_t* part_words, size_t* counters);
+void launch_sample(const SampleArgs& a, hipStream_t s);
+
 // y = LN(x [+ r]) * w + b ; if r != nullptr and sum_out != nullptr, sum_out = x + r
 void launch_layernorm(const void* x, const void* r, void* sum_out, const void* w, const void* b, void* y, int M,
                       int H, float eps, hipStream_t s);

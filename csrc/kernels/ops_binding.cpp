@@ -751,6 +751,72 @@ void decode_prologue(const at::Tensor& pos, const c10::optional<at::Tensor>& tok
                          dst[1], rb[1], (int)B, (int)T, (int)C, cur_stream());
 }
 
+// ---- token sampling (sample.hip)
+
+// (partial words, tickets, slices, slice length) of sample_tokens' workspace for B rows of V logits
+std::tuple<int64_t, int64_t, int64_t, int64_t> sample_sizes_b(int64_t B, int64_t V) {
+  TORCH_CHECK(B >= 1 && B <= 65535 && V >= 1 && V <= kSampleMaxV, "sample_tokens: needs 1 <= B <= 65535 and 1 <= V <= ",
+              kSampleMaxV, " (B ", B, ", V ", V, ")");
+  size_t pw = 0, nc = 0;
+  int S = 0, len = 0;
+  sample_sizes((int)B, (int)V, &pw, &nc);
+  sample_slices((int)B, (int)V, &S, &len);
+  return {(int64_t)pw, (int64_t)nc, (int64_t)S, (int64_t)len};
+}
+
+void sample_tokens(const at::Tensor& logits, int64_t V, int64_t T, const at::Tensor& pos, const at::Tensor& tokens,
+                   int64_t C, const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
+                   const at::Tensor& seed, int64_t request, const c10::optional<at::Tensor>& prompt_len,
+                   const c10::optional<at::Tensor>& eos, const c10::optional<at::Tensor>& done,
+                   const at::Tensor& next_out, const at::Tensor& stats, const at::Tensor& part,
+                   const at::Tensor& cnt) {
+  const int64_t B = pos.numel();
+  check_bf16(logits, "logits");
+  check_rows(logits, "logits");
+  TORCH_CHECK(T >= 1 && C >= 1 && B >= 1, "sample_tokens: B, T, C");
+  const auto sz = sample_sizes_b(B, V);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) == B * T && logits.size(1) >= V && logits.stride(0) % 8 == 0 &&
+                  logits.stride(0) >= (V + 7) / 8 * 8 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_tokens: logits must be [B*T][>= V], 16-byte aligned rows whose stride is a multiple of 8 and "
+              "covers V rounded up to 8");
+  TORCH_CHECK(B * T * logits.stride(0) < (1ll << 40), "sample_tokens: logits too large");
+  check_i32(pos, B, "pos");
+  check_i32(tokens, B * C, "tokens");
+  check_i32(top_k, B, "top_k");
+  check_i32(next_out, B, "next_out");
+  for (auto* p : {&temperature, &top_p})
+    TORCH_CHECK(p->is_cuda() && p->scalar_type() == at::kFloat && p->is_contiguous() && p->numel() == B,
+                "sample_tokens: temperature and top_p must be contiguous fp32 GPU tensors of ", B, " elements");
+  TORCH_CHECK(seed.is_cuda() && seed.scalar_type() == at::kLong && seed.numel() == 1,
+              "sample_tokens: seed must be an int64 GPU tensor of one element");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == B * 4 &&
+                  reinterpret_cast<uintptr_t>(stats.data_ptr()) % 16 == 0,
+              "sample_tokens: stats must be a contiguous 16-byte aligned fp32 GPU tensor [B][4]");
+  if (prompt_len.has_value()) check_i32(*prompt_len, B, "prompt_len");
+  if (eos.has_value()) check_i32(*eos, 1, "eos");
+  if (done.has_value()) check_i32(*done, B, "done");
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kInt && part.is_contiguous() &&
+                  part.numel() >= std::get<0>(sz) && reinterpret_cast<uintptr_t>(part.data_ptr()) % 16 == 0,
+              "sample_tokens: partials must be a contiguous 16-byte aligned int32 GPU tensor of >= ", std::get<0>(sz),
+              " elements");
+  TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == at::kInt && cnt.is_contiguous() && cnt.numel() >= std::get<1>(sz),
+              "sample_tokens: tickets must be a contiguous int32 GPU tensor of >= ", std::get<1>(sz), " elements");
+  TORCH_CHECK(request >= 0 && request < (1ll << 31), "sample_tokens: request ordinal");
+  SampleArgs a{};
+  a.logits = logits.data_ptr(), a.ld = (int)logits.stride(0);
+  a.V = (int)V, a.B = (int)B, a.T = (int)T, a.C = (int)C;
+  a.pos = pos.data_ptr<int>(), a.tokens = tokens.data_ptr<int>();
+  a.temperature = temperature.data_ptr<float>(), a.top_k = top_k.data_ptr<int>(), a.top_p = top_p.data_ptr<float>();
+  a.seed = reinterpret_cast<const long long*>(seed.data_ptr<int64_t>());
+  a.request = (int)request;
+  a.prompt_len = prompt_len.has_value() ? prompt_len->data_ptr<int>() : nullptr;
+  a.eos = eos.has_value() ? eos->data_ptr<int>() : nullptr;
+  a.done = done.has_value() ? done->data_ptr<int>() : nullptr;
+  a.next_out = next_out.data_ptr<int>(), a.stats = stats.data_ptr<float>();
+  a.part = reinterpret_cast<unsigned*>(part.data_ptr<int>()), a.cnt = cnt.data_ptr<int>();
+  launch_sample(a, cur_stream());
+}
+
 std::vector<at::Tensor> norm(const at::Tensor& x_in, const at::Tensor& w, const c10::optional<at::Tensor>& b,
                              double eps, const c10::optional<at::Tensor>& residual, bool rms,
                              const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& sum_out) {
@@ -1606,6 +1672,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("decode_prologue", &decode_prologue, py::arg("pos"), py::arg("tokens"), py::arg("tok_out"), py::arg("T"),
         py::arg("C"), py::arg("tables"), py::arg("outs"));
+  m.def("sample_sizes", &sample_sizes_b, py::arg("B"), py::arg("V"));
+  m.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("V"), py::arg("T"), py::arg("pos"),
+        py::arg("tokens"), py::arg("C"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("seed"),
+        py::arg("request"), py::arg("prompt_len"), py::arg("eos"), py::arg("done"), py::arg("next_out"),
+        py::arg("stats"), py::arg("part"), py::arg("cnt"));
   m.def("norm", &norm, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5,
         py::arg("residual") = py::none(), py::arg("rms") = false, py::arg("out") = py::none(),
         py::arg("sum_out") = py::none());

@@ -15,6 +15,9 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
   elastic   run with device-loss injection: a worker dies, the DAG is re-planned onto the
             surviving devices and the step is re-executed
   models    list the model presets
+  generate  generate tokens from synthetic prompts on one device: a decode plan whose step ends in
+            the sampling launch (``runtime.plan(generate=True)``); prints one JSON line with the
+            token ids, the steps and the tokens per second
 
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
@@ -364,6 +367,42 @@ def cmd_models(a) -> int:
     return 0
 
 
+def cmd_generate(a) -> int:
+    import torch
+
+    from .parallel import runtime
+    from .parallel.executor import synthetic_tokens
+
+    gpu = a.device != "cpu" and torch.cuda.is_available()
+    dev = torch.device("cuda:0") if gpu else torch.device("cpu")
+    if a.kv_cache is None:
+        raise SystemExit("generate needs --kv-cache C")
+    if a.prompt_len < 1 or a.new < 1 or a.prompt_len + a.new > a.kv_cache:
+        raise SystemExit(f"--prompt-len {a.prompt_len} + --new {a.new} must be positive and fit --kv-cache {a.kv_cache}")
+    p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
+                     kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True)
+    store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
+    ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
+    prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
+    ex.set_sampling(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed)
+    ex.set_prompts("@tokens", prompts)
+    ex.step()  # (derives weights, tunes nothing new afterwards)
+    captured = ex.capture() if gpu and not a.no_graph else False
+    ex.set_prompts("@tokens", prompts)
+    if gpu:
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tokens = ex.generate(a.new)
+    dt = time.perf_counter() - t0
+    steps = a.prompt_len - 1 + a.new
+    print(json.dumps({"model": a.model, "device": str(dev), "batch": a.batch, "kv_cache": a.kv_cache,
+                      "kv_dtype": a.kv_dtype, "prompt_len": a.prompt_len, "new": a.new, "temperature": a.temperature,
+                      "top_k": a.top_k, "top_p": a.top_p, "seed": a.seed, "graph": bool(captured), "steps": steps,
+                      "step_ms": round(dt / steps * 1e3, 4), "tokens_per_s": round(a.batch * steps / dt, 2),
+                      "prompts": prompts, "tokens": tokens}))
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m distributed_llm_scheduler_amd",
                                  description="MI355X-native memory-constrained DAG scheduler + executor")
@@ -420,6 +459,22 @@ def main(argv: Optional[List[str]] = None) -> int:
     el.set_defaults(fn=cmd_elastic)
     m = sub.add_parser("models", help="list model presets")
     m.set_defaults(fn=cmd_models)
+    g = sub.add_parser("generate", help="generate tokens on one device with on-device sampling")
+    g.add_argument("--model", default="gpt2")
+    g.add_argument("--kv-cache", type=int, default=None, metavar="C", help="positions per sequence (required)")
+    g.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
+    g.add_argument("--prompt-len", type=int, default=8, metavar="L", help="synthetic prompt tokens per sequence")
+    g.add_argument("--new", type=int, default=16, metavar="N", help="tokens to generate per sequence")
+    g.add_argument("--batch", type=int, default=1)
+    g.add_argument("--temperature", type=float, default=0.0, help="0 = greedy")
+    g.add_argument("--top-k", type=int, default=0, help="0 = off")
+    g.add_argument("--top-p", type=float, default=1.0, help=">= 1 = off")
+    g.add_argument("--seed", type=int, default=0)
+    g.add_argument("--scheduler", default="EFT")
+    g.add_argument("--hbm-cap-gb", type=float, default=288.0)
+    g.add_argument("--device", default="auto", choices=["auto", "cpu"])
+    g.add_argument("--no-graph", action="store_true")
+    g.set_defaults(fn=cmd_generate)
     a = ap.parse_args(argv)
     return a.fn(a)
 

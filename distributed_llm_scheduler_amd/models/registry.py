@@ -128,6 +128,35 @@ def check_kv_dtype(kv_dtype: str, kv_cache: "int | None") -> None:
         raise ValueError(f"kv_dtype={kv_dtype!r} needs a KV cache (kv_cache=C)")
 
 
+def check_generate(generate: bool, seq: int, kv_cache: "int | None") -> None:
+    """What on-device token sampling (``generate=True``) needs of a plan."""
+    if not generate:
+        return
+    if kv_cache is None:
+        raise ValueError("generate=True needs a KV cache (kv_cache=C): the sampler feeds the token stream of "
+                         "decode steps")
+    if seq != 1:
+        raise ValueError(f"generate=True needs seq=1, got {seq}: a step of T > 1 tokens would consume positions "
+                         "whose tokens are not generated yet")
+
+
+def sample_slices(B: int, V: int):
+    """(workgroups per row, elements per workgroup) of the sampling kernel (csrc/kernels/sample.hip
+    ``sample_slices``), for its workspace's bytes."""
+    S = max(1, min(64, -(-V // 8192), 512 // max(B, 1)))
+    length = -(-(-(-V // 8)) // S) * 8
+    return -(-V // length), length
+
+
+def sampler_state_bytes(op) -> int:
+    """Bytes a marked LM head (``attrs["sample"]``) keeps next to the caches: temperature, top_k,
+    top_p, prompt_len, done and next per sequence, stats [B][4], seed, eos, and the kernel's
+    workspace (264 words per workgroup of a row, one ticket per row), each padded to 256."""
+    B, V = op.out_shape[0], op.out_shape[-1]
+    al = lambda n: (n + 255) // 256 * 256  # noqa: E731
+    return 6 * al(4 * B) + al(16 * B) + al(8) + al(4) + al(4 * B * sample_slices(B, V)[0] * 264) + al(4 * B)
+
+
 def kv_cache_bytes(op, dtype_bytes: int = 2) -> int:
     """Bytes of an attention node's K and V caches: 2 * B * C * n_kv_head * head_dim * dtype_bytes;
     with ``attrs["kv_dtype"] == "fp8"`` 2 * B * C * n_kv_head * (head_dim + 4): one e4m3 byte per
@@ -170,7 +199,7 @@ def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_mo
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
           tp: int = 1, sp: int = 1, weight_dtype: str = "bf16", act_dtype: str = "bf16",
           kv_cache: "int | None" = None,
-          kv_dtype: str = "bf16") -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          kv_dtype: str = "bf16", generate: bool = False) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
@@ -188,8 +217,11 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     ``act_dtype="fp8"`` (the grouped kernel is W4A8). ``kv_cache=C``: ``seq`` is the number of new
     tokens per step and every attention node keeps a KV cache of C positions (:func:`add_kv_cache`).
     ``kv_dtype="fp8"`` (needs ``kv_cache``; independent of ``weight_dtype`` / ``act_dtype``): the
-    caches hold e4m3 bytes and one fp32 scale per (position, KV head) (:func:`kv_cache_bytes`)."""
+    caches hold e4m3 bytes and one fp32 scale per (position, KV head) (:func:`kv_cache_bytes`).
+    ``generate=True`` (needs ``kv_cache`` and ``seq == 1``): every request's ``lm_head`` op carries
+    ``attrs["sample"]``, the request's ordinal, and the executor samples the next token after it."""
     check_kv_dtype(kv_dtype, kv_cache)
+    check_generate(generate, seq, kv_cache)
     known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
     if weight_dtype not in known:
         raise ValueError(f"weight_dtype must be one of {known}, got {weight_dtype!r}")
@@ -227,6 +259,10 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))
     if kv_cache is not None:
         add_kv_cache(tasks, batch, seq, kv_cache, cost_model, kv_dtype)
+    if generate:
+        for t in tasks:
+            if t.op is not None and t.op.kind == "lm_head":
+                t.op.attrs["sample"] = int(t.id.split("/", 1)[0][1:]) if replicas > 1 else 0
     groups = param_groups(cfg)
     if tp > 1:
         from .transforms import tensor_parallel

@@ -829,6 +829,171 @@ def decode_prologue(pos, T, C, tokens=None, tok_out=None, tables=(), outs=()):
         o.copy_(t[p.reshape(-1)])
 
 
+# ---------------------------------------------------------- token sampling
+# The contract (README "Generating tokens"): greedy at temperature 0; otherwise weights
+# exp((l - l_max)/tau), top-k and top-p by whole value classes, and a Philox4x32-10 draw against the
+# cumulative weight in index order. Both paths write stats[b] = (theta, Z, weight before the token,
+# the token's weight) and apply the stream rule to ``tokens[b][pos[b] + T]``.
+
+SAMPLE_MAX_V = 1 << 20
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11): four 32-bit counter words, two key words -> four words."""
+    c0, c1, c2, c3 = (int(c) & 0xFFFFFFFF for c in counter)
+    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed: int, request: int, b: int, n: int) -> float:
+    """The draw of sequence ``b`` of request ``request`` at position ``n``: 24 bits in [0, 1)."""
+    seed &= (1 << 64) - 1
+    return (philox4x32_10((n, b, request, 0), (seed & 0xFFFFFFFF, seed >> 32))[0] >> 8) * 2.0 ** -24
+
+
+def sample_slices(B: int, V: int):
+    """(workgroups per row, elements per workgroup) of the GPU kernel for B rows of V logits."""
+    return tuple(ext().sample_sizes(int(B), int(V))[2:])
+
+
+def sample_workspace_sizes(B: int, V: int):
+    """(int32 partial words, int32 tickets) of ``sample_tokens``' workspace."""
+    return tuple(ext().sample_sizes(int(B), int(V))[:2])
+
+
+def sample_workspace(B, V, device):
+    """The workspace of ``sample_tokens``: (partials, tickets), allocated once by the caller (never
+    inside a captured step); the tickets start at zero and the launch resets them. The CPU path
+    needs none."""
+    if torch.device(device).type != "cuda":
+        return None
+    pw, nc = ext().sample_sizes(int(B), int(V))[:2]
+    return (torch.empty(max(pw, 4), dtype=torch.int32, device=device),
+            torch.zeros(max(nc, 1), dtype=torch.int32, device=device))
+
+
+def _sample_check(logits, V, T, pos, tokens, C, temperature, top_k, top_p, seed, request, prompt_len, eos, done,
+                  next_out, stats):
+    """The argument checks both paths of ``sample_tokens`` go through; returns B."""
+    def bad(msg):
+        raise ValueError("sample_tokens: " + msg)
+
+    dev = logits.device
+    B = pos.numel()
+    if not (1 <= V <= SAMPLE_MAX_V and T >= 1 and C >= 1 and B >= 1):
+        bad(f"needs 1 <= V <= {SAMPLE_MAX_V}, T >= 1, C >= 1 and at least one sequence (V {V}, T {T}, C {C}, B {B})")
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < V \
+            or logits.stride(1) != 1:
+        bad(f"logits must be bf16 [B*T][>= V] with contiguous rows (B {B}, T {T}, V {V}, got {tuple(logits.shape)})")
+    if logits.stride(0) % 8 or logits.stride(0) < (V + 7) // 8 * 8:
+        bad("the logits' row stride must be a multiple of 8 that covers V rounded up to 8")
+    if not 0 <= int(request) < 1 << 31:
+        bad(f"request ordinal {request}")
+
+    def vec(t, n, dtype, name):
+        if t is None:
+            return
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != n or not t.is_contiguous() \
+                or t.device != dev:
+            bad(f"{name} must be a contiguous {dtype} tensor of {n} elements on {dev}")
+
+    vec(pos, B, torch.int32, "pos")
+    vec(tokens, B * C, torch.int32, "tokens")
+    vec(temperature, B, torch.float32, "temperature")
+    vec(top_k, B, torch.int32, "top_k")
+    vec(top_p, B, torch.float32, "top_p")
+    vec(prompt_len, B, torch.int32, "prompt_len")
+    vec(done, B, torch.int32, "done")
+    vec(next_out, B, torch.int32, "next_out")
+    vec(stats, B * 4, torch.float32, "stats")
+    if isinstance(seed, torch.Tensor):
+        vec(seed, 1, torch.int64, "seed")
+    elif not isinstance(seed, int):
+        bad("seed must be an int or an int64 tensor of one element")
+    if isinstance(eos, torch.Tensor):
+        vec(eos, 1, torch.int32, "eos")
+    elif not isinstance(eos, int):
+        bad("eos must be an int or an int32 tensor of one element")
+    return B
+
+
+def _sample_row_ref(l, tau, k, p, u):
+    """One row of the contract in fp64 torch: (token, (theta, Z, before, weight))."""
+    V = l.numel()
+    lmax = l.max()
+    if not tau > 0:
+        return int((l == lmax).nonzero()[0]), (float(lmax), 1.0, 0.0, 1.0)
+    w = torch.exp((l - lmax) / tau)
+    theta = torch.topk(l, k).values[-1] if 0 < k < V else torch.tensor(-math.inf, dtype=l.dtype)
+    if p < 1:
+        kept = l >= theta
+        vals, inv = torch.unique(l[kept], return_inverse=True)  # ascending
+        cw = torch.zeros(vals.numel(), dtype=l.dtype).index_add_(0, inv, w[kept]).flip(0).cumsum(0)
+        reached = (cw >= p * cw[-1]).nonzero()
+        theta = vals.flip(0)[int(reached[0]) if reached.numel() else vals.numel() - 1]
+    kept = l >= theta
+    wk = torch.where(kept, w, torch.zeros_like(w))
+    cum = wk.cumsum(0)
+    Z = cum[-1]
+    hit = (kept & (cum > u * Z)).nonzero()
+    tok = int(hit[0]) if hit.numel() else int(kept.nonzero()[-1])
+    return tok, (float(theta), float(Z), float(cum[tok] - wk[tok]), float(wk[tok]))
+
+
+def sample_tokens(logits, V, T, pos, tokens, C, temperature, top_k, top_p, seed, request=0, prompt_len=None, eos=-1,
+                  done=None, next_out=None, stats=None, workspace=None):
+    """Choose the token at position ``n = pos[b] + T`` of every sequence from row ``b*T + T-1`` of
+    ``logits`` (bf16 [B*T][>= V], V valid columns) and feed it back: ``tokens[b][n] = next[b]``
+    where ``n >= prompt_len[b]`` and ``n < C``; inside the prompt ``next[b] = tokens[b][n]`` and
+    nothing is written; a finished sequence (``done[b]``) goes on with ``eos``. ``temperature``,
+    ``top_k``, ``top_p`` are tensors [B]; ``seed`` (int, or int64 [1]) and ``eos`` (int, or int32
+    [1]) may live on the device so that a captured launch follows them. Returns (next, stats).
+    GPU: sample.hip with ``workspace`` from ``sample_workspace``. CPU: fp64 torch."""
+    B = _sample_check(logits, V, T, pos, tokens, C, temperature, top_k, top_p, seed, request, prompt_len, eos, done,
+                      next_out, stats)
+    dev = logits.device
+    if next_out is None:
+        next_out = torch.empty(B, dtype=torch.int32, device=dev)
+    if stats is None:
+        stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    if _gpu(logits):
+        if workspace is None:
+            raise ValueError("sample_tokens needs the workspace of sample_workspace on the GPU")
+        if not isinstance(seed, torch.Tensor):
+            s64 = seed & ((1 << 64) - 1)
+            seed = torch.tensor([s64 - (1 << 64) if s64 >> 63 else s64], dtype=torch.int64, device=dev)
+        if not isinstance(eos, torch.Tensor):
+            eos = torch.tensor([eos], dtype=torch.int32, device=dev)
+        ext().sample_tokens(logits, int(V), int(T), pos, tokens, int(C), temperature, top_k, top_p, seed,
+                            int(request), prompt_len, eos, done, next_out, stats, workspace[0], workspace[1])
+        return next_out, stats
+    seed_i = int(seed.item()) if isinstance(seed, torch.Tensor) else seed
+    eos_i = int(eos.item()) if isinstance(eos, torch.Tensor) else eos
+    stream = tokens.view(B, C)
+    st = stats.view(B, 4)
+    for b in range(B):
+        n = int(pos[b]) + T
+        tok, row_stats = _sample_row_ref(logits[b * T + T - 1, :V].double(), float(temperature[b]), int(top_k[b]),
+                                         float(top_p[b]), sample_uniform(seed_i, int(request), b, n))
+        st[b] = torch.tensor(row_stats, dtype=torch.float64).float()
+        if n < (int(prompt_len[b]) if prompt_len is not None else 0):
+            if 0 <= n < C:
+                tok = int(stream[b, n])
+        else:
+            if done is not None and int(done[b]):
+                tok = eos_i
+            if done is not None and eos_i >= 0 and tok == eos_i:
+                done[b] = 1
+            if 0 <= n < C:
+                stream[b, n] = tok
+        next_out[b] = tok
+    return next_out, stats
+
+
 def gelu(x, out=None):
     if _gpu(x):
         return ext().gelu(x.contiguous(), out)

@@ -1553,7 +1553,8 @@ class DAGExecutor:
         """One kernel group. With KV caches (_setup_kv) the first group of a request on this rank
         also gathers the step's tokens and position-table rows at ``pos`` (one launch), and its
         last group that reads ``pos`` advances it by T — inside the group, so a captured step or
-        segment replays both."""
+        segment replays both. A sampling LM head (plan generate=True) reads ``pos`` too, so the
+        advance then comes after its group."""
         for st in self._kv_first.get(i, ()):
             self._kv_prologue(st)
         self._run_group_body(ins)
@@ -1618,6 +1619,8 @@ class DAGExecutor:
         elif k in ("linear", "lm_head"):
             self._gemm(self._flat(self._x(src)), W["w"], W.get("b"), norm, act=act, residual=residual,
                        out=self._flat(out), stats_out=st_out)
+            if k == "lm_head" and "sample" in a and self._kv:
+                self._sample(self._kv[_kv_prefix(head.id)], self._flat(out))
         elif k == "attention":
             x = self._flat(self._x(src))
             M = x.shape[0]
@@ -2352,6 +2355,9 @@ class DAGExecutor:
             return self._capture()
         saved = {k: (st["pos"].clone() if st["pos"] is not None else None, list(st["len"]))
                  for k, st in self._kv.items()}
+        # a generating plan's warm-up steps also write the stream and the eos flags
+        kept = {k: (st["tokens"].clone(), st["done"].clone()) for k, st in self._kv.items()
+                if st["sample"] is not None}
         self._kv_hold = True
         try:
             return self._capture()
@@ -2362,6 +2368,9 @@ class DAGExecutor:
                 if pos is not None:
                     self._kv[k]["pos"].copy_(pos)
                 self._kv[k]["len"] = lens
+            for k, (tok, done) in kept.items():
+                self._kv[k]["tokens"].copy_(tok)
+                self._kv[k]["done"].copy_(done)
             self._sync()
 
     def _capture(self) -> bool:
@@ -2749,6 +2758,7 @@ class DAGExecutor:
         self._kv_last: Dict[int, list] = {}  # ... -> states whose pos advances after it
         self._kv_full = self.kv_slab = self._kv_ws = None
         self._kv_hold = False
+        self._generates = False  # the plan samples tokens (runtime.plan generate=True)
         self.kv_capacity: Optional[int] = None
         cached = [t for t in self.tasks.values() if t.op is not None and t.op.kind == "attention"
                   and "kv_cache" in t.op.attrs]
@@ -2768,7 +2778,12 @@ class DAGExecutor:
                 B, T = t.op.out_shape[0], t.op.out_shape[1]
                 self._kv[_kv_prefix(t.id)] = dict(prefix=_kv_prefix(t.id), B=B, T=T, len=[0] * B, pos=None,
                                                   tokens=None, tok_g=None, wpe_g=None, wpe=None, cos=None,
-                                                  sin=None, cos_g=None, sin_g=None, input=None)
+                                                  sin=None, cos_g=None, sin_g=None, input=None, name=None,
+                                                  sample=None, plen=[0] * B)
+            if t.op is not None and t.op.kind == "embedding":
+                self._kv[_kv_prefix(t.id)]["name"] = t.op.inputs[0]  # (known on every rank, unlike "input")
+        self._generates = any(t.op is not None and t.op.kind == "lm_head" and "sample" in t.op.attrs
+                              for t in self.tasks.values())
         need, ws_need = [], [0, 0]  # (state / cache key, field, bytes) in slab order
 
         def want(key, field, shape, dtype):
@@ -2781,7 +2796,9 @@ class DAGExecutor:
             for tid in ins.group:
                 t = self.tasks[tid]
                 kind = t.op.kind
-                if kind not in ("embedding", "attention"):
+                if kind == "lm_head" and "sample" in t.op.attrs:
+                    kind = "sampler"
+                if kind not in ("embedding", "attention", "sampler"):
                     continue
                 pre = _kv_prefix(tid)
                 B, T = t.op.out_shape[0], t.op.out_shape[1]
@@ -2791,7 +2808,21 @@ class DAGExecutor:
                     self._kv_first.setdefault(i, []).append(st)
                 last[pre] = i
                 a = t.op.attrs
-                if kind == "embedding":
+                if kind == "sampler":
+                    # the sampler's parameters, flags and outputs per sequence, and its workspace
+                    V = t.op.out_shape[-1]
+                    st["sample"] = dict(V=V, request=int(a["sample"]))
+                    for fld, dt in (("temperature", torch.float32), ("top_k", torch.int32), ("top_p", torch.float32),
+                                    ("prompt_len", torch.int32), ("done", torch.int32), ("next", torch.int32)):
+                        want(pre, fld, (B,), dt)
+                    want(pre, "stats", (B, 4), torch.float32)
+                    want(pre, "seed", (1,), torch.int64)
+                    want(pre, "eos", (1,), torch.int32)
+                    if self.gpu:
+                        ws = ops.sample_workspace_sizes(B, V)
+                        want(pre, "s_part", (max(ws[0], 4),), torch.int32)
+                        want(pre, "s_cnt", (max(ws[1], 1),), torch.int32)
+                elif kind == "embedding":
                     st["input"] = t.op.inputs[0]
                     want(pre, "tokens", (B, C), torch.int32)
                     want(pre, "tok_g", (B * T,), torch.int32)
@@ -2848,6 +2879,20 @@ class DAGExecutor:
         for st in self._kv.values():
             if st["tokens"] is not None:  # the default stream: C synthetic tokens per sequence
                 st["tokens"].copy_(synthetic_tokens(st["input"], st["B"] * C, vocab, self.seed).view(st["B"], C))
+            if st["sample"] is not None:
+                if st["tokens"] is None:  # (runtime.plan refuses such a placement)
+                    raise RuntimeError(f"rank {self.prog.rank}: request {st['prefix'] or '0'!r} samples here but "
+                                       f"embeds elsewhere; a token is fed back on one GPU only")
+                st["top_p"].fill_(1.0)  # the slab is zero: greedy, no top-k, seed 0, nothing done, no prompt
+                st["eos"].fill_(-1)
+
+    def _sample(self, st: dict, logits: torch.Tensor) -> None:
+        """The launch after a marked LM head: the next token of every sequence into the stream."""
+        sm = st["sample"]
+        ops.sample_tokens(logits, sm["V"], st["T"], st["pos"], st["tokens"], self.kv_capacity, st["temperature"],
+                          st["top_k"], st["top_p"], st["seed"], request=sm["request"], prompt_len=st["prompt_len"],
+                          eos=st["eos"], done=st["done"], next_out=st["next"], stats=st["stats"],
+                          workspace=(st["s_part"], st["s_cnt"]) if self.gpu else None)
 
     def _kv_prologue(self, st: dict) -> None:
         tables, outs = [], []
@@ -2900,6 +2945,8 @@ class DAGExecutor:
             st["len"] = lens
             if st["pos"] is not None:  # (None: this rank runs no task of the request that reads pos)
                 st["pos"].copy_(torch.tensor(lens, dtype=torch.int32))
+            if st["sample"] is not None:
+                st["done"].zero_()
 
     def set_tokens(self, name: str, tokens) -> None:
         """The token stream [B][C] of external input ``name`` (e.g. ``"@tokens"``): step n consumes
@@ -2932,3 +2979,90 @@ class DAGExecutor:
                     c[b].copy_(q.view(torch.uint8).view(C, E))
                     cs[2 + i][b].copy_(sc.view(C, H).t())
         self.kv_reset(lengths)
+
+    # ------------------------------------------------------------- generation (plan generate=True)
+    def _gen_need(self) -> None:
+        self._kv_need()
+        if not self._generates:  # asked of the plan, as _kv_need
+            raise RuntimeError("this plan does not sample tokens (runtime.plan generate=True)")
+
+    def set_sampling(self, temperature=0.0, top_k=0, top_p=1.0, seed=0, eos=None) -> None:
+        """The sampling parameters of every request: ``temperature`` (0 = greedy), ``top_k`` (0 =
+        off) and ``top_p`` (>= 1 = off) as scalars or per-sequence lists, a 64-bit ``seed``, and
+        ``eos`` (None: no end token). Writes device memory only, so a captured step follows the
+        new values without re-capture. Call it on every rank alike."""
+        self._gen_need()
+        for st in self._kv.values():
+            B = st["B"]
+
+            def per(x, name, lo):
+                xs = [x] * B if isinstance(x, (int, float)) else list(x)
+                if len(xs) != B or any(not v >= lo for v in xs):
+                    raise ValueError(f"set_sampling: {name} wants a value >= {lo} or {B} of them, got {x!r}")
+                return xs
+
+            t, k, p = per(temperature, "temperature", 0.0), per(top_k, "top_k", 0), per(top_p, "top_p", 0.0)
+            if any(not v > 0 for v in p):
+                raise ValueError(f"set_sampling: top_p must be in (0, 1] (>= 1 = off), got {top_p!r}")
+            if not isinstance(seed, int) or (eos is not None and not isinstance(eos, int)):
+                raise ValueError("set_sampling: seed is an int, eos an int or None")
+            if st["sample"] is None:
+                continue
+            s64 = seed & ((1 << 64) - 1)
+            st["temperature"].copy_(torch.tensor(t, dtype=torch.float32))
+            st["top_k"].copy_(torch.tensor([int(v) for v in k], dtype=torch.int32))
+            st["top_p"].copy_(torch.tensor(p, dtype=torch.float32))
+            st["seed"].copy_(torch.tensor([s64 - (1 << 64) if s64 >> 63 else s64], dtype=torch.int64))
+            st["eos"].copy_(torch.tensor([-1 if eos is None else eos], dtype=torch.int32))
+
+    def set_prompts(self, name: str, prompts) -> None:
+        """The prompts of external input ``name`` (e.g. ``"@tokens"``): B ragged lists of token
+        ids, each 1 .. C long. Writes the stream prefixes and ``prompt_len`` where the stream
+        lives, then ``kv_reset()``: the next step starts every sequence at position 0, forces
+        its prompt and samples from the prompt's end on. Call it on every rank alike."""
+        self._gen_need()
+        vocab = self.cfg.vocab_size if self.cfg is not None else 50257
+        for st in self._kv.values():
+            if st["name"] != name:
+                continue
+            ps = [[int(x) for x in pr] for pr in prompts]
+            if len(ps) != st["B"] or any(not 1 <= len(pr) <= self.kv_capacity for pr in ps) \
+                    or any(not 0 <= x < vocab for pr in ps for x in pr):
+                raise ValueError(f"set_prompts: {st['B']} prompts of 1 .. {self.kv_capacity} token ids below "
+                                 f"{vocab} wanted")
+            st["plen"] = [len(pr) for pr in ps]
+            if st["sample"] is not None:
+                if self.gpu:
+                    self._sync()
+                for b, pr in enumerate(ps):
+                    st["tokens"][b, :len(pr)].copy_(torch.tensor(pr, dtype=torch.int32))
+                st["prompt_len"].copy_(torch.tensor(st["plen"], dtype=torch.int32))
+        self.kv_reset()
+
+    def generate(self, max_new_tokens: int):
+        """Run ``max(prompt_len) - 1 + max_new_tokens`` steps from the present lengths (after
+        ``set_prompts``: zero) and synchronise once at the end. Returns every sequence's first
+        ``max_new_tokens`` generated ids, [B] lists (or {request prefix: [B] lists} with several
+        requests) on the rank that holds the stream, None elsewhere. Raises before the first step
+        if the prompts and the new tokens do not fit the capacity C."""
+        self._gen_need()
+        n_new = int(max_new_tokens)
+        longest = max(max(st["plen"]) for st in self._kv.values())
+        if n_new < 1 or longest < 1:
+            raise ValueError("generate: set_prompts first, and ask for at least one new token")
+        steps = longest - 1 + n_new
+        C = self.kv_capacity
+        for st in self._kv.values():
+            if max(st["len"]) + steps * st["T"] > C or max(st["plen"]) + n_new > C:
+                raise RuntimeError(f"generate: prompts of up to {longest} tokens (lengths now {st['len']}) and "
+                                   f"{n_new} new tokens need {steps} steps and do not fit the KV cache "
+                                   f"capacity {C}")
+        for _ in range(steps):
+            self.step()
+        if self.gpu:
+            self._sync()
+        out = {k: [st["tokens"][b, n:n + n_new].tolist() for b, n in enumerate(st["plen"])]
+               for k, st in self._kv.items() if st["sample"] is not None}
+        if not out:
+            return None
+        return out[""] if list(out) == [""] else out

@@ -45,6 +45,8 @@ class Plan:
     # plan(kv_cache=C): bytes of the KV caches of the attention tasks each rank runs (they persist
     # across steps, next to the parameter and activation arenas); [] without a cache
     kv_cache_bytes: List[int] = field(default_factory=list)
+    # plan(generate=True): bytes of the sampler's state per rank; [] without it
+    sampler_bytes: List[int] = field(default_factory=list)
 
     def owner(self, tid: str) -> Optional[int]:
         """Rank holding task ``tid``'s output (a merged request resolves to its group)."""
@@ -70,7 +72,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          node_speeds: Optional[Sequence[float]] = None, link_bw_gbps: float = 153.0,
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
-         act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16") -> Plan:
+         act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
+         generate: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -147,6 +150,17 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     ``Plan.kv_cache_bytes`` then count. The step appends quantised rows and attends on the bytes
     (attn_decode_fp8.hip).
 
+    ``generate=True`` (with ``kv_cache`` and ``seq == 1`` only; anything else raises ``ValueError``
+    that says why): the decode step ends in a sampling launch (``ops.sample_tokens``) that writes
+    the next token of every sequence into the token stream the next step embeds, so the captured
+    step generates text (``DAGExecutor.set_prompts`` / ``set_sampling`` / ``generate``). Every
+    request's ``lm_head`` op carries ``attrs["sample"]``; after placement its ``lm_head`` and
+    ``embedding`` tasks must sit on one GPU (``world=1``, ``replica``, a ``scheduler`` placement
+    that co-locates them) — ``ValueError`` names the two GPUs otherwise (``pipeline`` over more than
+    one GPU): a token fed back across ranks is not supported. The sampler's state
+    (``registry.sampler_state_bytes``, ``Plan.sampler_bytes``) counts towards the cap check next to
+    the caches. The key enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -178,6 +192,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_kv_dtype(kv_dtype, kv_cache)
     if kv_dtype != "bf16":  # (only when not the default, as kv_cache)
         args["kv_dtype"] = kv_dtype
+    registry.check_generate(generate, seq, kv_cache)
+    if generate:  # (only when set: plans saved without it still resume, and stay as they were)
+        args["generate"] = True
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -193,7 +210,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
                                         sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache,
-                                        kv_dtype=kv_dtype)
+                                        kv_dtype=kv_dtype, generate=generate)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
 
     def place_under(caps_now: Sequence[float]) -> Plan:
@@ -269,6 +286,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                 over = _kv_over_cap(p, caps_gb)
         if over:
             raise ValueError(over)
+    if generate:
+        _check_feedback_placement(p)
     p.stats = plan_stats(p)
     return p
 
@@ -277,18 +296,38 @@ def _kv_over_cap(p: Plan, caps_gb: Sequence[float]) -> Optional[str]:
     """Sets ``p.kv_cache_bytes`` (per rank: the caches of the attention tasks placed there) and
     says which GPU, if any, cannot hold its parameter arena, activation arena and caches together:
     caches persist across tasks, unlike activations."""
-    per_rank = [0] * p.world
+    per_rank, sampler = [0] * p.world, [0] * p.world
     for t in p.tasks:
         if t.op is not None and t.op.kind == "attention" and t.id in p.placement:
             per_rank[p.placement[t.id]] += registry.kv_cache_bytes(t.op)
+        if t.op is not None and t.op.kind == "lm_head" and "sample" in t.op.attrs and t.id in p.placement:
+            sampler[p.placement[t.id]] += registry.sampler_state_bytes(t.op)
     p.kv_cache_bytes = per_rank
+    p.sampler_bytes = sampler if any(sampler) else []
     for r, pr in enumerate(p.programs):
         cap = int(caps_gb[r] * 1e9)
-        if pr.param_arena_bytes + pr.act_arena_bytes + per_rank[r] > cap:
+        if pr.param_arena_bytes + pr.act_arena_bytes + per_rank[r] + sampler[r] > cap:
             return (f"GPU {r}: parameter arena {pr.param_arena_bytes / 1e9:.6f} GB + activation arena "
-                    f"{pr.act_arena_bytes / 1e9:.6f} GB + KV caches {per_rank[r] / 1e9:.6f} GB exceed its cap of "
-                    f"{cap / 1e9:.6f} GB")
+                    f"{pr.act_arena_bytes / 1e9:.6f} GB + KV caches {per_rank[r] / 1e9:.6f} GB"
+                    + (f" + sampler state {sampler[r] / 1e9:.6f} GB" if sampler[r] else "")
+                    + f" exceed its cap of {cap / 1e9:.6f} GB")
     return None
+
+
+def _check_feedback_placement(p: Plan) -> None:
+    """plan(generate=True): the sampler writes the token stream its request's embedding reads, on
+    one GPU; a token fed back across ranks is not supported."""
+    emb = {t.id.rsplit("/", 1)[0] if "/" in t.id else "": t.id for t in p.tasks
+           if t.op is not None and t.op.kind == "embedding"}
+    for t in p.tasks:
+        if t.op is None or t.op.kind != "lm_head" or "sample" not in t.op.attrs:
+            continue
+        e = emb.get(t.id.rsplit("/", 1)[0] if "/" in t.id else "")
+        a, b = p.placement.get(t.id), p.placement.get(e)
+        if a is None or b is None or a != b:
+            raise ValueError(f"generate=True: {t.id} runs on GPU {a} and {e} on GPU {b}; the sampled token is fed "
+                             f"back on one GPU only (world=1, placement='replica', or a placement that keeps a "
+                             f"request's embedding and LM head together)")
 
 
 def real_time_s(t: Task, param_bytes: Dict[str, int]) -> float:
@@ -348,6 +387,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["kv_cache"] = (saved.get("kv_cache"), args.get("kv_cache"))
     if saved.get("kv_dtype", "bf16") != args.get("kv_dtype", "bf16"):
         mismatch["kv_dtype"] = (saved.get("kv_dtype", "bf16"), args.get("kv_dtype", "bf16"))
+    if saved.get("generate", False) != args.get("generate", False):
+        mismatch["generate"] = (saved.get("generate", False), args.get("generate", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -541,6 +582,7 @@ def plan_stats(p: Plan) -> Dict:
         "param_peak_gb_per_rank": [pr.param_peak_bytes / 1e9 for pr in p.programs],
         "act_arena_gb_per_rank": [pr.act_arena_bytes / 1e9 for pr in p.programs],
         **({"kv_cache_gb_per_rank": [b / 1e9 for b in p.kv_cache_bytes]} if p.kv_cache_bytes else {}),
+        **({"sampler_gb_per_rank": [b / 1e9 for b in p.sampler_bytes]} if p.sampler_bytes else {}),
         # parameter bytes re-filled per steady-state step (evict/reload traffic of the plan)
         "refill_gb_per_step_per_rank": [steady_fill_bytes(pr, p.param_bytes) / 1e9 for pr in p.programs],
         # of which received from a peer GPU's arena over xGMI (RCCL p2p) instead of the host
