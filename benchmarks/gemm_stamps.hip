@@ -1,9 +1,12 @@
 // In-kernel phase timing of one LDS-DMA GEMM config (diagnostic executable): compiles
-// csrc/kernels/gemm_glds_impl.h (configs 34, 13, 24, 27, 17, 45, 25, 22) into this translation unit
+// csrc/kernels/gemm_glds_impl.h (configs 34, 13, 24, 27, 17, 45, 25, 22, and the wave-private
+// rings 120..123: W x S = 8 x 2, 4 x 3, 6 x 2, 12 x 1) into this translation unit
 // with DLS_STAMP recording s_memrealtime (100 MHz) per workgroup at: tile start, after the main
 // loop (1), after the K groups' fragments are summed or, on the one-pass configs (Cfg::ONE_PASS),
 // handed over through LDS (7), after the output image is in LDS (2; the one-pass finish has no
-// image and never stamps it), after the stores (3).
+// image and never stamps it), after the stores (3). On the wave-private rings stamp 1 is WAVE 0's
+// own K loop (the waves do not meet inside it) and stamp 7 follows the kernel's one barrier, so
+// "main loop" + "K groups > LDS" is the figure to set against a K-grouped config's.
 //
 // The epilogue mode attaches the operands a model step attaches (none: a bare GEMM):
 //   res     bias + residual + stats_out            (GPT-2 out-proj, fc2)
@@ -15,7 +18,7 @@
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -Icsrc/kernels \
 //         benchmarks/gemm_stamps.hip -o gpubin/gemm_stamps
-//   gpubin/gemm_stamps <cfg> <M> <N> <K> [none|res|lngelu|ln]
+//   gpubin/gemm_stamps <cfg> <M> <N> <K> [none|res|lngelu|ln] [stream_pol]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +46,19 @@ DLS_GLDS_DEFINE(25)
 DLS_GLDS_DEFINE(22)
 // splitk = 1 only: the split-K reduce launcher of the library is stubbed out below
 static bool launch_gemm_glds_local(const GemmArgs& a, int cfg, const float* colsum, int ln_mode) {
+  if (cfg >= 120) {
+    const int waves = cfg == 120 ? 8 : cfg == 121 ? 4 : cfg == 122 ? 6 : cfg == 123 ? 12 : 0;
+    const bool ok = private_takes(waves, a, 1, ln_mode != 0, false);
+    if (!ok) {
+      fprintf(stderr, "config %d does not take this shape / epilogue\n", cfg);
+      exit(2);
+    }
+    if (cfg == 120) launch_private<8, 2>(a, 0);
+    else if (cfg == 121) launch_private<4, 3>(a, 0);
+    else if (cfg == 122) launch_private<6, 2>(a, 0);
+    else launch_private<12, 1>(a, 0);
+    return false;
+  }
   switch (cfg) {
     case 13: return glds_launch_cfg13(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
     case 24: return glds_launch_cfg24(a, 1, nullptr, 0, colsum, ln_mode, 1e-5f, nullptr, false);
@@ -94,6 +110,7 @@ int main(int argc, char** argv) {
   GemmArgs g{};
   g.A = A; g.lda = K; g.W = W; g.ldw = K; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.alpha = 1.f;
   g.config = cfg;
+  g.stream_pol = argc > 6 ? atoi(argv[6]) : 0;
   if (res) {
     g.bias = B; g.R = R; g.ldr = N; g.stats_out = stats;
   } else if (ln) {

@@ -1734,10 +1734,10 @@ using C47 = Cfg<128, 128, 2, 2, 2, 0, 1, 1, 0, 2>;
 
 // the Mixtral down tile's taller form (busiest expert per layer: 149-227 routed rows,
 // profiles/r6_mixtral/rows_vs_time.txt): 192 -> 256 rows (config 14; the grouped kernel keeps
-// 241 VGPRs, no scratch). The gate/up tile's (160 -> 224 rows, wave 112 x 64) spilled 68 VGPRs
-// in the grouped kernel: not instantiated.
-// gate/up (160 x 256): 224 x 256 (wave 112 x 64, split rings 2 x 28 KiB A + 3 x 32 KiB W) — the
-// grouped kernel spills 68 VGPRs with it (a 320 x 128 half-panel form spilled 132-172)
+// 241 VGPRs, no scratch).
+// gate/up (160 x 256): 224 x 256 (wave 112 x 64, split rings 2 x 28 KiB A + 3 x 32 KiB W),
+// instantiated below — the grouped kernel spills 68 VGPRs with it (a 320 x 128 half-panel form
+// spilled 132-172)
 template <>
 struct TallTile<C44> {
   using type = Cfg<224, 256, 2, 4, 2, 0, 1>;
@@ -1783,6 +1783,277 @@ void grouped(const GemmArgs& a, int n_groups, const int* offsets, const unsigned
                      nullptr, a.ldw, (bf16*)a.C, a.ldc, nullptr, nullptr, 0,
                      const_cast<float*>(reinterpret_cast<const float*>(a_rows)), a.M, a.N, a.K, a.act, a.alpha,
                      n_groups, tiles_n, 1, a.K, nullptr, 0, 1e-5f, offsets, a.compact_rows, ep);
+}
+
+// ---- Wave-private rings: a barrier-free K loop for the 32 x 48 tiles (kGemmPrivate ids) ----
+//
+// The K-grouped tiles above move every stage with the whole block: each K super-step all waves
+// wait, pass one s_barrier and issue their share of the next stage together. Here each of the W
+// waves owns a contiguous slice of K and an LDS ring of its own (S slots of one 64-deep K-tile:
+// 80 rows x 128 B = 10 KiB, 4 DMA instructions for the A rows and 6 for the W rows), multiplies
+// the WHOLE 32 x 48 tile over its slice (FM = 2, FN = 3: 24 accumulator registers) and meets the
+// other waves only once, at the barrier of the finish. Ordering inside the loop is the wave's own:
+//  * RAW: a wave reads only bytes its own DMA instructions wrote, behind its own counted vmcnt
+//    wait (vmcnt retires in order). The barrier that rule asks for elsewhere is for OTHER readers
+//    of the staged bytes; there are none.
+//  * WAR: a slot is re-issued only behind an lgkmcnt(0) that follows the ds_reads of it (LDS
+//    returns in order: every read of the slot has delivered), pinned by sched_barrier(0) on both
+//    sides of the refill.
+// Every wave executes the same instruction counts whatever its slice holds, and no wave leaves
+// before the finish: the kernel's one barrier cannot be missed (the host refuses a K whose tiles
+// do not divide by W, and the grid is exactly the tile count — no idle block, no early return).
+template <int W_, int S_>
+struct PrivCfg {
+  static constexpr int W = W_, S = S_, BM = 32, BN = 48, BK = 64, CH = 8, FM = 2, FN = 3;
+  static constexpr int T = 64 * W, PW = (BM + BN) / 8;  // DMA instructions per K-tile
+  static constexpr int SLOT = (BM + BN) * CH;            // bf16x8 units of one K-tile image
+  static constexpr int RING = S * SLOT, LDS_UNITS = W * RING;
+  static constexpr int REG = FM * FN * 64;               // f32x4 records of a wave's fragments
+  static_assert(S >= 1 && PW * (S - 1) <= 63, "vmcnt range");
+  static_assert(LDS_UNITS * 16 <= 163840 && T <= 1024, "LDS budget, block size");
+  static_assert(REG <= RING, "a wave's fragment region lies inside its own ring");
+  static_assert(T >= BM * 8, "one 16-byte output segment per storing thread");
+};
+
+template <class P>
+__device__ __forceinline__ void mainloop_private(bf16x8* ring, const bf16* __restrict__ A, int lda,
+                                                 const bf16* __restrict__ W, int ldw, int M, int N, int m0, int n0,
+                                                 int kbeg, int nk, int lane, f32x4 (&acc)[P::FM][P::FN]) {
+  const bf16* src[P::PW];
+#pragma unroll
+  for (int j = 0; j < P::PW; ++j) {
+    const int row = 8 * j + (lane >> 3);
+    const int kofs = kbeg + ((lane & 7) ^ (row & 7)) * 8;
+    src[j] = row < P::BM ? A + (size_t)min(m0 + row, M - 1) * lda + kofs
+                         : W + (size_t)min(n0 + row - P::BM, N - 1) * ldw + kofs;
+  }
+  auto issue = [&](int kt, bf16x8* slot) {
+#pragma unroll
+    for (int j = 0; j < P::PW; ++j)
+      __builtin_amdgcn_global_load_lds((const void*)(src[j] + kt * P::BK),
+                                       (__attribute__((address_space(3))) void*)(slot + j * 64), 16, 0, 0);
+  };
+#pragma unroll
+  for (int s = 0; s < P::S; ++s)
+    if (s < nk) issue(s, ring + s * P::SLOT);
+  int sl = 0;
+  for (int kt = 0; kt < nk; ++kt) {
+    // tiles kt+1 .. kt+S-1 were issued after kt and may stay in flight (kt+S goes out below)
+    wait_tiles<P::PW, P::S - 1>(min(P::S - 1, nk - 1 - kt));
+    bf16x8* slot = ring + sl * P::SLOT;
+    const bf16x8* sA = slot;
+    const bf16x8* sB = slot + P::BM * P::CH;
+    bf16x8 af[2][P::FM], bw[2][P::FN];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int chunk = kk * 4 + (lane >> 4);
+#pragma unroll
+      for (int j = 0; j < P::FN; ++j) {
+        const int row = j * 16 + (lane & 15);
+        bw[kk][j] = sB[row * P::CH + (chunk ^ (row & 7))];
+      }
+#pragma unroll
+      for (int i = 0; i < P::FM; ++i) {
+        const int row = i * 16 + (lane & 15);
+        af[kk][i] = sA[row * P::CH + (chunk ^ (row & 7))];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the slot has returned (WAR)
+    __builtin_amdgcn_sched_barrier(0);
+    if (kt + P::S < nk) issue(kt + P::S, slot);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int i = 0; i < P::FM; ++i)
+#pragma unroll
+        for (int j = 0; j < P::FN; ++j) acc[i][j] = mfma16x16x32(bw[kk][j], af[kk][i], acc[i][j]);
+    sl = sl + 1 == P::S ? 0 : sl + 1;
+  }
+}
+
+// C = alpha * A @ W^T + bias (+ R), row statistics of the stored bf16 into stats_out: what GPT-2's
+// out-proj and fc2 attach. The finish is the one-pass finish of the K-grouped tiles with W regions:
+// each wave writes its six fp32 fragments into a region at the start of ITS OWN ring (its last
+// vmcnt(0) retired every DMA into that ring and its MFMAs consumed every read of it: no barrier
+// before the write), ONE barrier, and thread tid < 256 sums the W records of its 16-byte row
+// segment in ascending wave order, finishes and stores it — the same expression, operand
+// requests and store as glds_tile's one-pass finish.
+template <class P, int SPOL>
+__global__ __launch_bounds__(P::T, 1) void gemm_private_kernel(const bf16* __restrict__ A, int lda,
+                                                               const bf16* __restrict__ W, int ldw,
+                                                               bf16* __restrict__ Cp, int ldc,
+                                                               const bf16* __restrict__ bias,
+                                                               const bf16* __restrict__ R, int ldr,
+                                                               float* __restrict__ stats_out, int M, int N, int K,
+                                                               float alpha, int tiles_m) {
+  __shared__ bf16x8 smem[P::LDS_UNITS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int m0 = (tile % tiles_m) * P::BM, n0 = (tile / tiles_m) * P::BN;
+  DLS_STAMP(0)
+  const int nk = K / (P::BK * P::W);  // K-tiles of every wave's slice
+  bf16x8* ring = smem + wave * P::RING;
+  f32x4 acc[P::FM][P::FN];
+#pragma unroll
+  for (int i = 0; i < P::FM; ++i)
+#pragma unroll
+    for (int j = 0; j < P::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  mainloop_private<P>(ring, A, lda, W, ldw, M, N, m0, n0, wave * nk * P::BK, nk, lane, acc);
+  DLS_STAMP(1)
+  // the segment's operands, requested in one batch behind the wave's last vmcnt wait (range-checked
+  // buffer loads: rows past M and, with the vector forms, columns past N read zeros)
+  constexpr int BNC = P::BN / 8, BNP = 8;
+  const bool own = tid < P::BM * BNP;  // (wave-uniform: four whole waves)
+  const int rl = tid / BNP, cc = tid % BNP;
+  const int row = m0 + rl, col = n0 + cc * 8;
+  const bool pre_bvec = ((reinterpret_cast<uintptr_t>(bias) & 7) | (N & 3)) == 0;
+  const bool v16 = ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2)) & 15) == 0 &&
+                   (!R || ((reinterpret_cast<uintptr_t>(R) | ((uintptr_t)ldr * 2)) & 15) == 0);
+  const bool pre_res = R != nullptr && N >= 8 && v16 && ((size_t)(M + P::BM) * ldr * 2 < (1ull << 31));
+  // (a bias that is not 8-byte aligned, or N % 4 != 0, is read in place behind the barrier: a second
+  // batched form's registers would be written on this path behind the pending loads of the other)
+  u32x2 o_bv[2];  // pre_bvec: 4 bf16 each
+  u32x4 o_r;
+  if (own) {
+    constexpr int kRaw = 0x00020000;  // raw buffer, 32-bit data
+    if (bias && pre_bvec) {
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(bias), 0, N * 2, kRaw);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) o_bv[h] = __builtin_amdgcn_raw_buffer_load_b64(rs, col * 2 + h * 8, 0, 0);
+    }
+    if (pre_res) {
+      const auto rs =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(R), 0, (int)(((size_t)(M - 1) * ldr + N) * 2), kRaw);
+      o_r = __builtin_amdgcn_raw_buffer_load_b128(rs, (row * ldr + col) * 2, 0, 0);
+    }
+  }
+  // fragment records: glds_tile's one-pass layout with one wave per region (NW = 1)
+  f32x4* reg = reinterpret_cast<f32x4*>(ring);
+#pragma unroll
+  for (int i = 0; i < P::FM; ++i)
+#pragma unroll
+    for (int j = 0; j < P::FN; ++j) {
+      const int cl = j * 16 + (lane >> 4) * 4;
+      reg[(i * P::FN + j) * 64 + (lane & 48) + ((lane & 15) ^ (((cl >> 3) & 3) << 2))] = acc[i][j];
+    }
+  epi_barrier<true>();  // THE barrier: every wave's fragments are in LDS (operand requests stay in flight)
+  DLS_STAMP(7)
+  if (own) {
+    // (chunks past BNC read chunk BNC - 1 again and store nothing)
+    const int ccr = min(cc, BNC - 1), cl0 = ccr * 8;
+    const int rec = ((rl / 16) * P::FN + cl0 / 16) * 64 + (cl0 & 8) * 4 + ((rl & 15) ^ ((ccr & 3) << 2));
+    const f32x4* red = reinterpret_cast<const f32x4*>(smem);
+    f32x4 part_lo[P::W], part_hi[P::W];
+#pragma unroll
+    for (int w = 0; w < P::W; ++w) {
+      part_lo[w] = red[w * P::RING + rec];
+      part_hi[w] = red[w * P::RING + rec + 16];
+    }
+    f32x4 lo = part_lo[0], hi = part_hi[0];
+#pragma unroll
+    for (int w = 1; w < P::W; ++w) {
+      lo += part_lo[w];
+      hi += part_hi[w];
+    }
+    float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (bias) {
+      if (pre_bvec) {
+        uint32_t w[8];  // (a bf16 is the high half of its fp32)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          consume_from_here(o_bv[h]);
+          const uint32_t p0 = o_bv[h][0], p1 = o_bv[h][1];
+          w[4 * h + 0] = p0 << 16;
+          w[4 * h + 1] = p0 & 0xffff0000u;
+          w[4 * h + 2] = p1 << 16;
+          w[4 * h + 3] = p1 & 0xffff0000u;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bv[e] = col + e < N ? __uint_as_float(w[e]) : 0.f;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < N) bv[e] = bf2f(bias[col + e]);
+      }
+    }
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = f2bf(alpha * (e < 4 ? lo[e & 3] : hi[e & 3]) + bv[e]);
+    if (pre_res) consume_from_here(o_r);
+    // the residual add, the store and the row statistics of what was stored (glds_tile: store_segment)
+    float s1 = 0.f, s2 = 0.f;
+    if (cc < BNC && row < M && col < N) {
+      if (v16 && col + 8 <= N) {
+        if (R) {
+          const bf16x8 r8 = pre_res ? *reinterpret_cast<const bf16x8*>(&o_r)
+                                    : *reinterpret_cast<const bf16x8*>(R + (size_t)row * ldr + col);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(o[e]) + bf2f(r8[e]));
+        }
+        store16_pol<SPOL>(Cp, ((size_t)row * ldc + col) * 2, *reinterpret_cast<const u32x4*>(&o));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float y = bf2f(o[e]);
+          s1 += y;
+          s2 += y * y;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          if (col + e >= N) continue;
+          float x = bf2f(o[e]);
+          if (R) x += bf2f(R[(size_t)row * ldr + col + e]);
+          const bf16 ob = f2bf(x);
+          Cp[(size_t)row * ldc + col + e] = ob;
+          const float y = bf2f(ob);
+          s1 += y;
+          s2 += y * y;
+        }
+      }
+    }
+    if (stats_out) {
+#pragma unroll
+      for (int o_ = 1; o_ < BNP; o_ <<= 1) {
+        s1 += __shfl_xor(s1, o_, 64);
+        s2 += __shfl_xor(s2, o_, 64);
+      }
+      if (cc == 0 && row < M) {
+        atomicAdd(stats_out + 2 * row, s1);
+        atomicAdd(stats_out + 2 * row + 1, s2);
+      }
+    }
+  }
+  DLS_STAMP(3)
+}
+
+// Whether the wave-private family takes this launch: plain 32 x 48 tiles of the whole K, nothing
+// attached but bias / residual / stats_out / alpha (the callers fall back to the table's previous
+// config, or refuse a forced id).
+inline bool private_takes(int waves, const GemmArgs& a, int splitk, bool folded_norm, bool ranged) {
+  return waves > 0 && a.K > 0 && a.K % (64 * waves) == 0 && splitk <= 1 && !folded_norm && !ranged &&
+         a.act == ACT_NONE && a.rope.cols == 0 && !a.ext_stats;
+}
+
+template <int W_, int S_>
+void launch_private(const GemmArgs& a, hipStream_t s) {
+  using P = PrivCfg<W_, S_>;
+  const int tiles_m = (a.M + P::BM - 1) / P::BM, tiles_n = (a.N + P::BN - 1) / P::BN;
+  dim3 grid(tiles_m * tiles_n), block(P::T);
+#define DLS_PK(POL_)                                                                                               \
+  hipLaunchKernelGGL((gemm_private_kernel<P, POL_>), grid, block, 0, s, (const bf16*)a.A, a.lda, (const bf16*)a.W, \
+                     a.ldw, (bf16*)a.C, a.ldc, (const bf16*)a.bias, (const bf16*)a.R, a.ldr, a.stats_out, a.M, a.N, \
+                     a.K, a.alpha, tiles_m)
+  // (the output stores' cache policy, GemmArgs::stream_pol bits 1 and 2, as launch<C> maps them:
+  // policy stores carry 32-bit byte offsets, outputs of 2 GB and more keep the default stores)
+  switch ((size_t)a.M * a.ldc * 2 < (1ull << 31) ? a.stream_pol & 7 : 0) {
+    case 2: case 3: DLS_PK(kPolStream); break;
+    case 4: case 5: DLS_PK(kPolWT); break;
+    default: DLS_PK(0);
+  }
+#undef DLS_PK
 }
 
 }  // namespace

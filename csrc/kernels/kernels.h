@@ -101,6 +101,17 @@ size_t gemm_glds_workspace_bytes(int M, int N, int splitk);
 bool launch_gemm_glds(const GemmArgs& a, int cfg, int splitk, void* workspace, hipStream_t s,
                       const float* ln_colsum = nullptr, int ln_mode = 0, float ln_eps = 1e-5f,
                       const int* rows = nullptr);
+// Wave-private rings (gemm_private.hip; gemm_glds_impl.h: mainloop_private): a family of its own
+// for the skinny 32 x 48 tiles, ids kGemmPrivate + {0, 1, 2, 3} = W waves x S ring slots of
+// 8 x 2, 4 x 3, 6 x 2, 12 x 1. It takes plain launches only — the whole K in one block with
+// K % (64 W) == 0, no activation, folded norm, RoPE, SwiGLU, split-K or row range; bias, residual,
+// stats_out and alpha are what it attaches (gemm_private_takes; the launcher launches nothing and
+// returns false otherwise).
+constexpr int kGemmPrivate = 120, kGemmPrivateCount = 4;
+int gemm_private_waves(int cfg);  // W of a family id, 0 for any other id
+bool gemm_private_takes(const GemmArgs& a, int cfg, int splitk, bool folded_norm, bool ranged);
+bool launch_gemm_private(const GemmArgs& a, int cfg, hipStream_t s);
+
 // Grouped MoE-expert GEMM: E groups in ONE launch (grid = E x column tiles). Group g multiplies
 // rows [offsets[g], offsets[g+1]) of A by its own weight (w_ptrs[g], [N][K], ldw = a.ldw) and
 // writes them either at the same rows of a.C (c_ptrs == nullptr) or compactly to rows

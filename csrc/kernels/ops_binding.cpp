@@ -63,7 +63,9 @@ at::Tensor as2d(const at::Tensor& t) { return t.dim() == 2 ? t : t.reshape({-1, 
 // splitk: 0 auto (LDS-DMA path), otherwise forced.
 // config: -1 auto, 0..gemm_glds_num_configs()-1 LDS-DMA kernel (| kGemmPersist: persistent),
 // kRegStage..kRegStage+3 register-staged kernel (ids that would also read as persistent 36..39;
-// persistent launches of configs >= 36 have no id, larger ones are refused).
+// persistent launches of configs >= 36 have no id, larger ones are refused),
+// kGemmPrivate..+kGemmPrivateCount-1 the wave-private-ring family (kernels.h): it refuses — here, with
+// an error — every launch it does not take; ops.linear falls back before it gets here.
 // act ACT_SWIGLU: W rows interleave gate/up blocks of 16 (see common.h); the output is N/2 wide.
 // rows (int32[2] on device): only rows [rows[0], rows[1]) of A / out take part (MoE expert ranges).
 constexpr int64_t kRegStage = 100;
@@ -80,8 +82,10 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 double norm_eps, int64_t stream_pol) {
   check_bf16(a_in, "A");
   check_bf16(w, "W");
-  TORCH_CHECK(config < kRegStage + 4, "unknown GEMM config ", config, " (register-staged configs are ", kRegStage,
-              "..", kRegStage + 3, ")");
+  const bool priv = gemm_private_waves((int)config) != 0;
+  TORCH_CHECK(config < kRegStage + 4 || priv, "unknown GEMM config ", config, " (register-staged configs are ",
+              kRegStage, "..", kRegStage + 3, ", wave-private rings ", kGemmPrivate, "..",
+              kGemmPrivate + kGemmPrivateCount - 1, ")");
   at::Tensor a = as2d(a_in);
   check_rows(a, "A");
   check_rows(w, "W");
@@ -186,7 +190,7 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 "RoPE epilogue: D % 4 == 0, whole heads, LDS-DMA kernel, no activation / SwiGLU / row range");
     g.rope = RopeArgs{rope_cos->data_ptr<float>(), rope_sin->data_ptr<float>(), (int)rope_S, (int)rope_D,
                       (int)rope_cols};
-    if (config >= kRegStage) config = -1;
+    if (config >= kRegStage && !priv) config = -1;
   }
   const bool glds_ok = (K % 64 == 0);
   const float* csp = nullptr;
@@ -196,6 +200,15 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                     ln_colsum->numel() == N,
                 "fused norm-GEMM needs fp32 ln_colsum [N]");
     csp = ln_colsum->data_ptr<float>();
+  }
+  if (priv) {
+    TORCH_CHECK(!compact_rows && gemm_private_takes(g, (int)config, (int)splitk, ln_mode != 0, rowp != nullptr),
+                "GEMM config ", config, " (wave-private rings, ", gemm_private_waves((int)config),
+                " waves) takes plain launches only: K % ", 64 * gemm_private_waves((int)config),
+                " == 0, no activation, folded norm, RoPE, SwiGLU, split-K or row range");
+    TORCH_CHECK(launch_gemm_private(g, (int)config, cur_stream()), "GEMM config ", config, " refused the launch");
+    post_norm(false);
+    return c;
   }
   if (ln_mode != 0 || swiglu || rowp || stats_out.has_value()) {
     TORCH_CHECK(glds_ok, "this epilogue needs the LDS-DMA kernel (K % 64 == 0)");
@@ -1641,6 +1654,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_w4a8_grouped_pick", &gemm_w4a8_grouped_pick);
   m.attr("REGSTAGE") = kRegStage;
   m.attr("PERSIST") = kGemmPersist;
+  m.attr("PRIVATE") = kGemmPrivate;
+  m.attr("PRIVATE_COUNT") = kGemmPrivateCount;
+  m.def("gemm_private_waves", &gemm_private_waves);
   m.def("gemm_pick_config", &gemm_pick_config);
   m.def("gemm_glds_num_configs", &gemm_glds_num_configs);
   m.def("gemm_glds_kstep", &gemm_glds_kstep);

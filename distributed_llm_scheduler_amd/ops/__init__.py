@@ -285,6 +285,8 @@ def linear(x, w, bias=None, act=None, residual=None, alpha=1.0, out=None, rows=N
                         o2.mul_(alpha)
                 return o2.view(shp) if out is None else out
             cfg, sk = tuning.lookup_fused(rows_hint or M, w.shape[0], w.shape[1], tuning.tag(a, rows is not None))
+        # (a wave-private choice the family refuses for this epilogue: the same tile's K-grouped config)
+        cfg, sk = tuning.resolve_private((cfg, sk), w.shape[1], a, rows is not None, rope is not None)
         rc, rs_, rS, rD, rcols = rope if rope is not None else (None, None, 1, 2, 0)
         y = ext().gemm(x, w, bias, residual, a, float(alpha), out, cfg, sk, None, 0, 1e-5, rows, bool(compact),
                        rc, rs_, int(rS), int(rD), int(rcols), stats_out, None,
@@ -581,7 +583,7 @@ def linear_norm(x, w_derived, colsum, bias_derived, mode, eps=1e-5, act=None, re
                        colsum[n0:n1], m, float(eps), None, False, None, None, 1, 2, 0, None, ext_stats,
                        stream_pol=pol)
         return out
-    cfg, sk = tuning.lookup_fused(M, N, K, tuning.tag(a))
+    cfg, sk = tuning.resolve_private(tuning.lookup_fused(M, N, K, tuning.tag(a)), K, a, folded=True)
     if ext_stats is None:
         sk = 1
         if 0 <= cfg < tuning.REGSTAGE and tuning.kstep(cfg) != 64:

@@ -39,6 +39,32 @@ LIB = 200       # the vendor library (hipBLASLt through torch.mm): OFF unless DL
                 # runs on the HIP kernels). Default: every GEMM runs on the hand-written kernels,
                 # and a table entry naming LIB resolves to the best HIP candidate (lookup)
 VENDOR = os.environ.get("DLS_ALLOW_VENDOR_GEMM", "0") == "1"
+# Wave-private rings (csrc kernels.h kGemmPrivate): id -> waves W of the 32 x 48 tile's workgroup.
+# The family takes plain launches only (private_takes); a table entry naming it runs
+# PRIVATE_FALLBACK — the K-grouped config of the same tile, what the table held before — for a
+# launch the family refuses. (The ids are >= REGSTAGE: every variant / grouped / folded-norm path
+# that drops register-staged choices drops these too.)
+PRIVATE = 120
+PRIVATE_WAVES = {120: 8, 121: 4, 122: 6, 123: 12}
+PRIVATE_FALLBACK = (45, 1)
+
+
+def private_takes(cfg: int, K: int, sk: int = 1, act: int = 0, ranged: bool = False, rope: bool = False,
+                  folded: bool = False) -> bool:
+    """Does wave-private config ``cfg`` take this launch (csrc gemm_private_takes)? Every wave
+    owns K / W whole 64-deep K-tiles; bias, residual, stats_out and alpha are all it attaches."""
+    w = PRIVATE_WAVES.get(cfg, 0)
+    return w > 0 and K > 0 and K % (64 * w) == 0 and sk <= 1 and act == 0 and not (ranged or rope or folded)
+
+
+def resolve_private(choice: Tuple[int, int], K: int, act: int = 0, ranged: bool = False, rope: bool = False,
+                    folded: bool = False) -> Tuple[int, int]:
+    """A tuned choice as it is launched: a wave-private id stays if the family takes the launch,
+    else PRIVATE_FALLBACK; any other choice is returned as it is."""
+    cfg, sk = choice
+    if cfg not in PRIVATE_WAVES:
+        return choice
+    return (cfg, 1) if private_takes(cfg, K, sk, act, ranged, rope, folded) else PRIVATE_FALLBACK
 
 
 def _key(M: int, N: int, K: int, tg: str = "") -> str:

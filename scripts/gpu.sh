@@ -126,7 +126,10 @@ case "$job" in
       timeout -k 5 30 gpubin/gemm_stamps $shape >> $O/stamps.txt 2>&1 || { echo "FAILED $shape"; exit 3; }
     done
     # the GPT-2 step's own configs, bare and with the epilogue operands the step attaches
-    for shape in "45 512 768 768 res" "45 512 768 3072 res" "17 512 2304 768 ln" "17 512 3072 768 lngelu" "13 512 50304 768 ln"; do
+    # (120..123: the wave-private rings, W x S = 8 x 2, 4 x 3, 6 x 2, 12 x 1, beside config 45)
+    for shape in "45 512 768 768 res" "121 512 768 768 res" "122 512 768 768 res" "123 512 768 768 res" \
+                 "45 512 768 3072 res" "120 512 768 3072 res" "121 512 768 3072 res" "122 512 768 3072 res" \
+                 "123 512 768 3072 res" "17 512 2304 768 ln" "17 512 3072 768 lngelu" "13 512 50304 768 ln"; do
       s=($shape)
       for mode in none ${s[4]}; do
         timeout -k 5 30 gpubin/gemm_stamps ${s[0]} ${s[1]} ${s[2]} ${s[3]} $mode >> $O/stamps.txt 2>&1 || { echo "FAILED $shape $mode"; exit 3; }
