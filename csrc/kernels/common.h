@@ -21,6 +21,7 @@ typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -49,10 +50,37 @@ __device__ __forceinline__ void store8_pol(void* base, size_t off, u32x2 v) {
   }
 }
 
+// four bf16 at element index idx of C, with the aux bits a launcher resolved (store_pol_aux)
+__device__ __forceinline__ void store_bf16x4(bf16* C, size_t idx, bf16x4 o, int pol) {
+  const u32x2 v = *reinterpret_cast<const u32x2*>(&o);
+  if (pol == 16) store8_pol<16>(C, idx * 2, v);
+  else if (pol == 2) store8_pol<2>(C, idx * 2, v);
+  else store8_pol<0>(C, idx * 2, v);
+}
+// A launcher's store_pol argument (bit 2: write-through, bit 1: nt) -> aux bits. Policy stores
+// are buffer stores with 32-bit byte offsets from the output's base: outputs of 2 GB and more
+// keep the default stores.
+inline int store_pol_aux(size_t out_bytes, int store_pol) {
+  const int pol = out_bytes >= (1ull << 31) ? 0 : store_pol;
+  return (pol & 4) ? 16 : (pol & 2) ? 2 : 0;
+}
+
 #define DLS_WAVE 64
 
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
+
+// 8 e4m3 bytes -> 8 bf16 (exact)
+__device__ __forceinline__ bf16x8 cvt_e4m3x8(uint32_t lo, uint32_t hi) {
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false);
+  const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false);
+  const f32x2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  bf16x8 r;
+  r[0] = f2bf(a[0]); r[1] = f2bf(a[1]); r[2] = f2bf(b[0]); r[3] = f2bf(b[1]);
+  r[4] = f2bf(c[0]); r[5] = f2bf(c[1]); r[6] = f2bf(d[0]); r[7] = f2bf(d[1]);
+  return r;
+}
 
 __device__ __forceinline__ f32x4 mfma16x16x32(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);

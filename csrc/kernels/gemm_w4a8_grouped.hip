@@ -67,13 +67,6 @@ struct GW4Cfg {
   static_assert(PF >= 2 && AD >= 2 && PF % AD == 0 && PF % 2 == 0, "the K loop is unrolled PF times: static slots");
 };
 
-__device__ __forceinline__ void store_bf16x4(bf16* C, size_t idx, bf16x4 o, int pol) {
-  const u32x2 v = *reinterpret_cast<const u32x2*>(&o);
-  if (pol == 16) store8_pol<16>(C, idx * 2, v);
-  else if (pol == 2) store8_pol<2>(C, idx * 2, v);
-  else store8_pol<0>(C, idx * 2, v);
-}
-
 struct GW4Params {
   const uint8_t* A;  // e4m3 [.][lda bytes]
   int lda;
@@ -380,11 +373,8 @@ void launch_gemm_w4a8_grouped(const GemmW4A8GroupedArgs& a, hipStream_t s) {
   p.compact_rows = a.compact_rows;
   p.groups = a.n_groups;
   p.shared = a.shared_weights;
-  // policy stores are buffer stores with 32-bit byte offsets from the output's base: outputs
-  // of 2 GB and more keep the default stores
   const size_t out_rows = a.c_ptrs != nullptr ? (size_t)a.compact_rows : (size_t)a.R;
-  const int pol = out_rows * a.ldc * 2 >= (1ull << 31) ? 0 : a.store_pol;
-  p.pol = (pol & 4) ? 16 : (pol & 2) ? 2 : 0;
+  p.pol = store_pol_aux(out_rows * a.ldc * 2, a.store_pol);
   const bool sdw = a.K % BK == 0 && a.scales_aligned4;
   switch (a.config) {
     case 0: launch_cfg<GW4C0>(p, sdw, s); break;

@@ -27,11 +27,11 @@
 // Split-K (grid.z): each split writes an fp32 partial slab, a second kernel sums the slabs in
 // a fixed order and runs the epilogue — no atomics, bitwise reproducible.
 #include "common.h"
+#include "gemm_quant_host.h"
+#include "gemm_quant_reduce.h"
 #include "kernels.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BK = 64;
 constexpr int ACH = BK / 8;   // 16-byte chunks per A row of a slice
@@ -48,27 +48,9 @@ struct W8Cfg {
   static constexpr int STAGE = A_UNITS + W_UNITS;  // 16-byte units per buffer
   static_assert(FM >= 1 && FN >= 2 && FN % 2 == 0, "wave tile: whole gate/up fragment pairs");
   static_assert(WTN % 32 == 0, "a wave's columns start on a gate/up block pair");
+  static_assert(A_UNITS % T == 0 && W_UNITS % T == 0, "whole staging passes");
   static_assert(2 * STAGE * 16 <= 64 * 1024, "static LDS");
 };
-
-// 8 e4m3 bytes -> 8 bf16 (exact)
-__device__ __forceinline__ bf16x8 cvt_e4m3x8(uint32_t lo, uint32_t hi) {
-  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false);
-  const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
-  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false);
-  const f32x2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
-  bf16x8 r;
-  r[0] = f2bf(a[0]); r[1] = f2bf(a[1]); r[2] = f2bf(b[0]); r[3] = f2bf(b[1]);
-  r[4] = f2bf(c[0]); r[5] = f2bf(c[1]); r[6] = f2bf(d[0]); r[7] = f2bf(d[1]);
-  return r;
-}
-
-__device__ __forceinline__ void store_bf16x4(bf16* C, size_t idx, bf16x4 o, int pol) {
-  const u32x2 v = *reinterpret_cast<const u32x2*>(&o);
-  if (pol == 16) store8_pol<16>(C, idx * 2, v);
-  else if (pol == 2) store8_pol<2>(C, idx * 2, v);
-  else store8_pol<0>(C, idx * 2, v);
-}
 
 struct W8Params {
   const bf16* A;
@@ -85,6 +67,12 @@ struct W8Params {
   int tiles_m, tiles_n;
   int kper;  // K elements per split (a multiple of BK)
   int pol;   // store8_pol aux bits of the output stores (0, 2 nt, 16 write-through)
+};
+
+// the format to gemm_quant_reduce.h
+struct W8A16 {
+  using Params = W8Params;
+  static constexpr bool kRowScale = false, kColScale = true;
 };
 
 template <class G>
@@ -271,56 +259,10 @@ __global__ __launch_bounds__(G::T) void gemm_w8_kernel(const W8Params p) {
   }
 }
 
-// out = epilogue(sum over the split slabs, slab 0 first). VEC output columns per thread
-// (4 needs N % 4 == 0, NO % 4 == 0, ldc % 4 == 0, C 8-byte aligned; 1 takes anything).
-template <int VEC>
-__global__ __launch_bounds__(256) void gemm_w8_reduce_kernel(const W8Params p, int splitk) {
-  const bool sw = p.act == ACT_SWIGLU;
-  const int M = p.M, N = p.N, NO = sw ? N / 2 : N;
-  const int per_row = (NO + VEC - 1) / VEC;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)M * per_row) return;
-  const int row = (int)(idx / per_row), oc = (int)(idx % per_row) * VEC;
-  const size_t slab = (size_t)M * N;
-  float o[VEC];
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) {
-    const int c = oc + e;
-    // SwiGLU: output column c pairs weight rows 32b + j (gate) and 32b + 16 + j (up), c = 16b + j
-    const int col = sw ? (c / 16) * 32 + (c % 16) : c;
-    const float* P = p.part + (size_t)row * N + col;
-    float a = 0.f, u = 0.f;
-    for (int s = 0; s < splitk; ++s) {
-      a += P[s * slab];
-      if (sw) u += P[s * slab + 16];
-    }
-    float v = p.alpha * p.scale[col] * a + (p.bias ? bf2f(p.bias[col]) : 0.f);
-    if (sw) {
-      v = silu(v) * (p.alpha * p.scale[col + 16] * u + (p.bias ? bf2f(p.bias[col + 16]) : 0.f));
-    } else {
-      v = apply_act(v, p.act);
-    }
-    if (p.R) v += bf2f(p.R[(size_t)row * p.ldr + c]);
-    o[e] = v;
-  }
-  if constexpr (VEC == 4) {
-    bf16x4 ob;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ob[e] = f2bf(o[e]);
-    store_bf16x4(p.C, (size_t)row * p.ldc + oc, ob, p.pol);
-  } else {
-    p.C[(size_t)row * p.ldc + oc] = f2bf(o[0]);
-  }
-}
-
 using W8C0 = W8Cfg<128, 128, 2, 2>;
 using W8C1 = W8Cfg<64, 128, 2, 2>;
 using W8C2 = W8Cfg<64, 64, 2, 2>;
 using W8C3 = W8Cfg<32, 64, 2, 2>;
-constexpr int kNumCfg = 4;
-constexpr int kTileM[kNumCfg] = {128, 64, 64, 32};
-constexpr int kTileN[kNumCfg] = {128, 128, 64, 64};
-constexpr int kMaxSplit = 8;
 
 template <class G>
 void launch_cfg(W8Params p, int splitk, hipStream_t s) {
@@ -329,54 +271,21 @@ void launch_cfg(W8Params p, int splitk, hipStream_t s) {
   hipLaunchKernelGGL((gemm_w8_kernel<G>), dim3(p.tiles_m * p.tiles_n, 1, splitk), dim3(G::T), 0, s, p);
 }
 
-inline long blocks_for(int M, int N, int c) {
-  return (long)((M + kTileM[c] - 1) / kTileM[c]) * ((N + kTileN[c] - 1) / kTileN[c]);
-}
-
 }  // namespace
 
-int gemm_w8_num_configs() { return kNumCfg; }
+int gemm_w8_num_configs() { return quant_host::kNumCfg; }
 
 int gemm_w8_max_splitk(int cfg, int K) {
   (void)cfg;
-  const int kt = (K + BK - 1) / BK;
-  return kt < kMaxSplit ? (kt < 1 ? 1 : kt) : kMaxSplit;
+  return quant_host::max_splitk(K, BK);
 }
 
 void gemm_w8_pick(int M, int N, int K, int* cfg, int* splitk) {
-  // Fitted to the cold-weight measurements of the GPT-2 and Llama-3-8B layer shapes at M = 512
-  // (benchmarks/bench_gemm_w8.py, profiles/w8/gemm_w8.txt):
-  //  * 128 x 128 tiles when they alone cover the 256 CUs (gate/up, LM head);
-  //  * 128 x 128 tiles with a K split when the split grid fills whole rounds of the 512 blocks
-  //    resident at once (two per CU) and every split keeps >= 16 slices (Llama's wo and down
-  //    projections: 128 tiles x 4); a grid that ends in a mostly empty round loses more than
-  //    the split gains (Llama's QKV: 192 tiles);
-  //  * otherwise small tiles, several blocks per CU: 64 x 64 when that gives 512 blocks, else
-  //    32 x 64, K split while the grid is below 512 blocks and >= 8 slices per split remain.
-  const int kt = (K + BK - 1) / BK;
-  const long b0 = blocks_for(M, N, 0);
-  *cfg = 0;
-  *splitk = 1;
-  if (b0 >= 256) return;
-  if (M > 64)
-    for (int sk = 2; sk <= kMaxSplit; sk *= 2) {
-      if (kt / sk < 16) break;
-      const long rounds = (b0 * sk + 511) / 512;
-      if (b0 * sk >= 512 && b0 * sk * 10 >= rounds * 512 * 9) {
-        *splitk = sk;
-        return;
-      }
-    }
-  const int c = (M > 32 && blocks_for(M, N, 2) >= 512) ? 2 : 3;
-  const long blocks = blocks_for(M, N, c);
-  int sk = 1;
-  while (sk < kMaxSplit && blocks * sk < 512 && kt / (sk * 2) >= 8) sk *= 2;
-  *cfg = c;
-  *splitk = sk;
+  quant_host::pick(M, N, K, BK, 16, 8, cfg, splitk);
 }
 
 size_t gemm_w8_workspace_bytes(int M, int N, int splitk) {
-  return splitk > 1 ? (size_t)splitk * M * N * sizeof(float) : 0;
+  return quant_host::workspace_bytes(M, N, splitk);
 }
 
 void launch_gemm_w8(const GemmW8Args& a, hipStream_t s) {
@@ -396,18 +305,10 @@ void launch_gemm_w8(const GemmW8Args& a, hipStream_t s) {
   p.K = a.K;
   p.act = a.act;
   p.alpha = a.alpha;
-  const int NO = a.act == ACT_SWIGLU ? a.N / 2 : a.N;
-  // policy stores are buffer stores with 32-bit byte offsets from the output's base: outputs
-  // of 2 GB and more keep the default stores
-  const int pol = (size_t)a.M * a.ldc * 2 >= (1ull << 31) ? 0 : a.store_pol;
-  p.pol = (pol & 4) ? 16 : (pol & 2) ? 2 : 0;
-  const int kt = (a.K + BK - 1) / BK;
-  int splitk = a.splitk < 1 ? 1 : a.splitk;
-  if (splitk > kt) splitk = kt;
-  const int per = (kt + splitk - 1) / splitk;
-  splitk = (kt + per - 1) / per;  // no empty split
-  if (a.workspace == nullptr) splitk = 1;
-  p.kper = (splitk > 1 ? per : kt) * BK;
+  p.pol = store_pol_aux((size_t)a.M * a.ldc * 2, a.store_pol);
+  const quant_host::Split sp = quant_host::resolve_split(a.K, BK, a.splitk, a.workspace != nullptr);
+  const int splitk = sp.splitk;
+  p.kper = sp.kper;
   p.part = splitk > 1 ? a.workspace : nullptr;
   switch (a.config) {
     case 0: launch_cfg<W8C0>(p, splitk, s); break;
@@ -415,11 +316,5 @@ void launch_gemm_w8(const GemmW8Args& a, hipStream_t s) {
     case 2: launch_cfg<W8C2>(p, splitk, s); break;
     default: launch_cfg<W8C3>(p, splitk, s); break;
   }
-  if (splitk > 1) {
-    const bool vec = a.N % 4 == 0 && NO % 4 == 0 && a.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
-    const long n = (long)a.M * (vec ? NO / 4 : NO);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (vec) hipLaunchKernelGGL((gemm_w8_reduce_kernel<4>), grid, dim3(256), 0, s, p, splitk);
-    else hipLaunchKernelGGL((gemm_w8_reduce_kernel<1>), grid, dim3(256), 0, s, p, splitk);
-  }
+  if (splitk > 1) launch_quant_reduce<W8A16>(p, splitk, s);
 }

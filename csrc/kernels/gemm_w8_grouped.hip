@@ -29,7 +29,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // the weights' addresses come from a device array: without the global address space on the load
 // the compiler emits FLAT loads, which also count as LDS traffic — every wait for an LDS read
 // would then wait for the whole weight ring
@@ -55,25 +54,6 @@ struct GW8Cfg {
   static_assert(2 * A_UNITS * 16 <= 64 * 1024, "static LDS");
   static_assert(PF >= 2 && AD >= 2 && PF % AD == 0 && PF % 2 == 0, "the K loop is unrolled PF times: static slots");
 };
-
-// 8 e4m3 bytes -> 8 bf16 (exact)
-__device__ __forceinline__ bf16x8 cvt_e4m3x8(uint32_t lo, uint32_t hi) {
-  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false);
-  const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
-  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false);
-  const f32x2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
-  bf16x8 r;
-  r[0] = f2bf(a[0]); r[1] = f2bf(a[1]); r[2] = f2bf(b[0]); r[3] = f2bf(b[1]);
-  r[4] = f2bf(c[0]); r[5] = f2bf(c[1]); r[6] = f2bf(d[0]); r[7] = f2bf(d[1]);
-  return r;
-}
-
-__device__ __forceinline__ void store_bf16x4(bf16* C, size_t idx, bf16x4 o, int pol) {
-  const u32x2 v = *reinterpret_cast<const u32x2*>(&o);
-  if (pol == 16) store8_pol<16>(C, idx * 2, v);
-  else if (pol == 2) store8_pol<2>(C, idx * 2, v);
-  else store8_pol<0>(C, idx * 2, v);
-}
 
 struct GW8Params {
   const bf16* A;
@@ -347,11 +327,8 @@ void launch_gemm_w8_grouped(const GemmW8GroupedArgs& a, hipStream_t s) {
   p.compact_rows = a.compact_rows;
   p.groups = a.n_groups;
   p.shared = a.shared_weights;
-  // policy stores are buffer stores with 32-bit byte offsets from the output's base: outputs
-  // of 2 GB and more keep the default stores
   const size_t out_rows = a.c_ptrs != nullptr ? (size_t)a.compact_rows : (size_t)a.R;
-  const int pol = out_rows * a.ldc * 2 >= (1ull << 31) ? 0 : a.store_pol;
-  p.pol = (pol & 4) ? 16 : (pol & 2) ? 2 : 0;
+  p.pol = store_pol_aux(out_rows * a.ldc * 2, a.store_pol);
   switch (a.config) {
     case 0: launch_cfg<GW8C0>(p, s); break;
     case 1: launch_cfg<GW8C1>(p, s); break;

@@ -250,6 +250,91 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
   return c;
 }
 
+// One of the dense quantised GEMMs (gemm_w8.hip, gemm_w8a8.hip, gemm_w4a8.hip) to quant_gemm_common
+struct QuantGemmKind {
+  const char* name;  // in "unknown <name> GEMM config"
+  int (*num_configs)();
+  void (*pick)(int M, int N, int K, int* cfg, int* splitk);
+  int (*max_splitk)(int cfg, int K);
+  size_t (*workspace_bytes)(int M, int N, int splitk);
+};
+const QuantGemmKind kQuantW8{"fp8-weight", gemm_w8_num_configs, gemm_w8_pick, gemm_w8_max_splitk,
+                             gemm_w8_workspace_bytes};
+const QuantGemmKind kQuantW8A8{"fp8", gemm_w8a8_num_configs, gemm_w8a8_pick, gemm_w8a8_max_splitk,
+                               gemm_w8a8_workspace_bytes};
+const QuantGemmKind kQuantW4A8{"MXFP4", gemm_w4a8_num_configs, gemm_w4a8_pick, gemm_w4a8_max_splitk,
+                               gemm_w4a8_workspace_bytes};
+
+// What the three wrappers share once their operands are checked: the epilogue arguments, the
+// output (the caller's, checked, or a fresh one), the config and split-K resolution (-1 / 0 pick
+// by shape) and the split-K workspace (the caller's, checked, or a fresh one).
+struct QuantGemmCommon {
+  at::Tensor c, ws;
+  const void* bias = nullptr;
+  const void* R = nullptr;
+  int ldr = 0;
+  int cfg = 0, sk = 1;
+  float* workspace = nullptr;  // of ws when sk > 1
+};
+QuantGemmCommon quant_gemm_common(const QuantGemmKind& kind, const at::Tensor& a, int64_t M, int64_t N, int64_t K,
+                                  const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& residual,
+                                  int64_t act, const c10::optional<at::Tensor>& out, int64_t config, int64_t splitk,
+                                  const c10::optional<at::Tensor>& workspace) {
+  QuantGemmCommon q;
+  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
+  const bool swiglu = act == kActSwiglu;
+  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
+  const int64_t NO = swiglu ? N / 2 : N;
+  if (out.has_value()) {
+    q.c = as2d(*out);
+    check_bf16(q.c, "out");
+    TORCH_CHECK(q.c.device() == a.device() && q.c.size(0) == M && q.c.size(1) == NO && q.c.stride(1) == 1,
+                "out must be [M][N_out] with contiguous rows");
+  } else {
+    q.c = at::empty({M, NO}, a.options().dtype(at::kBFloat16));
+  }
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
+    q.bias = bias->data_ptr();
+  }
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
+    q.R = r.data_ptr();
+    q.ldr = (int)r.stride(0);
+  }
+  if (M == 0 || N == 0) return q;  // nothing to launch
+  q.cfg = (int)config;
+  q.sk = (int)splitk;
+  if (q.cfg < 0 || q.sk <= 0) {
+    int acfg, ask;
+    kind.pick((int)M, (int)N, (int)K, &acfg, &ask);
+    if (q.cfg < 0) {
+      q.cfg = acfg;
+      if (q.sk <= 0) q.sk = ask;
+    } else if (q.sk <= 0) {
+      q.sk = 1;
+    }
+  }
+  TORCH_CHECK(q.cfg < kind.num_configs(), "unknown ", kind.name, " GEMM config ", q.cfg);
+  q.sk = std::min(q.sk, kind.max_splitk(q.cfg, (int)K));
+  if (q.sk > 1) {
+    const int64_t need = (int64_t)kind.workspace_bytes((int)M, (int)N, q.sk) / 4;
+    if (workspace.has_value()) {
+      q.ws = *workspace;
+      TORCH_CHECK(q.ws.is_cuda() && q.ws.device() == a.device() && q.ws.scalar_type() == at::kFloat &&
+                      q.ws.is_contiguous() && q.ws.numel() >= need,
+                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
+    } else {
+      q.ws = at::empty({need}, a.options().dtype(at::kFloat));
+    }
+    q.workspace = q.ws.data_ptr<float>();
+  }
+  return q;
+}
+
 // W8A16 GEMM (gemm_w8.hip): wq e4m3 [N][K] (K contiguous), scale fp32 [N]. config / splitk: -1 / 0
 // pick by shape. workspace (fp32, optional): the split-K partial slabs — a caller inside a
 // hipGraph capture passes one it allocated before; otherwise the caching allocator provides it.
@@ -271,65 +356,14 @@ at::Tensor gemm_w8(const at::Tensor& a_in, const at::Tensor& wq, const at::Tenso
   TORCH_CHECK(scale.is_cuda() && scale.device() == a.device() && scale.scalar_type() == at::kFloat &&
                   scale.is_contiguous() && scale.numel() == N,
               "scale must be a contiguous fp32 [N] tensor on A's GPU");
-  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
-  const bool swiglu = act == kActSwiglu;
-  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
-  const int64_t NO = swiglu ? N / 2 : N;
-  at::Tensor c;
-  if (out.has_value()) {
-    c = as2d(*out);
-    check_bf16(c, "out");
-    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
-                "out must be [M][N_out] with contiguous rows");
-  } else {
-    c = at::empty({M, NO}, a.options());
-  }
-  const void* bptr = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
-    bptr = bias->data_ptr();
-  }
-  const void* rptr = nullptr;
-  int ldr = 0;
-  if (residual.has_value()) {
-    at::Tensor r = as2d(*residual);
-    check_bf16(r, "residual");
-    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
-    rptr = r.data_ptr();
-    ldr = (int)r.stride(0);
-  }
-  if (M == 0 || N == 0) return c;
-  int cfg = (int)config, sk = (int)splitk;
-  if (cfg < 0 || sk <= 0) {
-    int acfg, ask;
-    gemm_w8_pick((int)M, (int)N, (int)K, &acfg, &ask);
-    if (cfg < 0) {
-      cfg = acfg;
-      if (sk <= 0) sk = ask;
-    } else if (sk <= 0) {
-      sk = 1;
-    }
-  }
-  TORCH_CHECK(cfg < gemm_w8_num_configs(), "unknown fp8-weight GEMM config ", cfg);
-  sk = std::min(sk, gemm_w8_max_splitk(cfg, (int)K));
-  at::Tensor ws;
-  if (sk > 1) {
-    const int64_t need = (int64_t)gemm_w8_workspace_bytes((int)M, (int)N, sk) / 4;
-    if (workspace.has_value()) {
-      ws = *workspace;
-      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
-                      ws.is_contiguous() && ws.numel() >= need,
-                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
-    } else {
-      ws = at::empty({need}, a.options().dtype(at::kFloat));
-    }
-  }
+  const QuantGemmCommon q =
+      quant_gemm_common(kQuantW8, a, M, N, K, bias, residual, act, out, config, splitk, workspace);
+  if (M == 0 || N == 0) return q.c;
   GemmW8Args g{a.data_ptr(), (int)a.stride(0), wq.data_ptr(), (int)wq.stride(0), scale.data_ptr<float>(),
-               c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K, (int)act, (float)alpha,
-               cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+               q.c.data_ptr(), (int)q.c.stride(0), q.bias, q.R, q.ldr, (int)M, (int)N, (int)K, (int)act, (float)alpha,
+               q.cfg, q.sk, q.workspace, (int)store_pol};
   launch_gemm_w8(g, cur_stream());
-  return c;
+  return q.c;
 }
 
 // W8A8 GEMM (gemm_w8a8.hip): xq e4m3 [M][K] with fp32 row scales, wq e4m3 [N][K] with fp32 channel
@@ -357,66 +391,14 @@ at::Tensor gemm_w8a8(const at::Tensor& xq_in, const at::Tensor& xscale, const at
   TORCH_CHECK(scale.is_cuda() && scale.device() == a.device() && scale.scalar_type() == at::kFloat &&
                   scale.is_contiguous() && scale.numel() == N,
               "scale must be a contiguous fp32 [N] tensor on xq's GPU");
-  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
-  const bool swiglu = act == kActSwiglu;
-  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
-  const int64_t NO = swiglu ? N / 2 : N;
-  const auto bf = a.options().dtype(at::kBFloat16);
-  at::Tensor c;
-  if (out.has_value()) {
-    c = as2d(*out);
-    check_bf16(c, "out");
-    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
-                "out must be [M][N_out] with contiguous rows");
-  } else {
-    c = at::empty({M, NO}, bf);
-  }
-  const void* bptr = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
-    bptr = bias->data_ptr();
-  }
-  const void* rptr = nullptr;
-  int ldr = 0;
-  if (residual.has_value()) {
-    at::Tensor r = as2d(*residual);
-    check_bf16(r, "residual");
-    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
-    rptr = r.data_ptr();
-    ldr = (int)r.stride(0);
-  }
-  if (M == 0 || N == 0) return c;
-  int cfg = (int)config, sk = (int)splitk;
-  if (cfg < 0 || sk <= 0) {
-    int acfg, ask;
-    gemm_w8a8_pick((int)M, (int)N, (int)K, &acfg, &ask);
-    if (cfg < 0) {
-      cfg = acfg;
-      if (sk <= 0) sk = ask;
-    } else if (sk <= 0) {
-      sk = 1;
-    }
-  }
-  TORCH_CHECK(cfg < gemm_w8a8_num_configs(), "unknown fp8 GEMM config ", cfg);
-  sk = std::min(sk, gemm_w8a8_max_splitk(cfg, (int)K));
-  at::Tensor ws;
-  if (sk > 1) {
-    const int64_t need = (int64_t)gemm_w8a8_workspace_bytes((int)M, (int)N, sk) / 4;
-    if (workspace.has_value()) {
-      ws = *workspace;
-      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
-                      ws.is_contiguous() && ws.numel() >= need,
-                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
-    } else {
-      ws = at::empty({need}, a.options().dtype(at::kFloat));
-    }
-  }
+  const QuantGemmCommon q =
+      quant_gemm_common(kQuantW8A8, a, M, N, K, bias, residual, act, out, config, splitk, workspace);
+  if (M == 0 || N == 0) return q.c;
   GemmW8A8Args g{a.data_ptr(), (int)a.stride(0), xscale.data_ptr<float>(), wq.data_ptr(), (int)wq.stride(0),
-                 scale.data_ptr<float>(), c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K,
-                 (int)act, (float)alpha, cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+                 scale.data_ptr<float>(), q.c.data_ptr(), (int)q.c.stride(0), q.bias, q.R, q.ldr, (int)M, (int)N,
+                 (int)K, (int)act, (float)alpha, q.cfg, q.sk, q.workspace, (int)store_pol};
   launch_gemm_w8a8(g, cur_stream());
-  return c;
+  return q.c;
 }
 
 // W4A8 GEMM (gemm_w4a8.hip): xq e4m3 [M][K] with fp32 row scales, wq uint8 [N][K/2] (two e2m1 per
@@ -444,66 +426,14 @@ at::Tensor gemm_w4a8(const at::Tensor& xq_in, const at::Tensor& xscale, const at
   TORCH_CHECK(ws_in.is_cuda() && ws_in.device() == a.device() && ws_in.scalar_type() == at::kByte &&
                   ws_in.dim() == 2 && ws_in.size(0) == N && ws_in.size(1) == K / 32 && ws_in.stride(1) == 1,
               "the block scales must be a uint8 [N][K/32] tensor with contiguous rows on xq's GPU");
-  TORCH_CHECK(act >= 0 && act <= kActSwiglu, "unknown activation ", act);
-  const bool swiglu = act == kActSwiglu;
-  TORCH_CHECK(!swiglu || N % 32 == 0, "SwiGLU epilogue needs gate/up rows interleaved in blocks of 16 (N % 32 == 0)");
-  const int64_t NO = swiglu ? N / 2 : N;
-  const auto bf = a.options().dtype(at::kBFloat16);
-  at::Tensor c;
-  if (out.has_value()) {
-    c = as2d(*out);
-    check_bf16(c, "out");
-    TORCH_CHECK(c.device() == a.device() && c.size(0) == M && c.size(1) == NO && c.stride(1) == 1,
-                "out must be [M][N_out] with contiguous rows");
-  } else {
-    c = at::empty({M, NO}, bf);
-  }
-  const void* bptr = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N, "bias must be contiguous [N]");
-    bptr = bias->data_ptr();
-  }
-  const void* rptr = nullptr;
-  int ldr = 0;
-  if (residual.has_value()) {
-    at::Tensor r = as2d(*residual);
-    check_bf16(r, "residual");
-    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1, "residual must be [M][N_out]");
-    rptr = r.data_ptr();
-    ldr = (int)r.stride(0);
-  }
-  if (M == 0 || N == 0) return c;
-  int cfg = (int)config, sk = (int)splitk;
-  if (cfg < 0 || sk <= 0) {
-    int acfg, ask;
-    gemm_w4a8_pick((int)M, (int)N, (int)K, &acfg, &ask);
-    if (cfg < 0) {
-      cfg = acfg;
-      if (sk <= 0) sk = ask;
-    } else if (sk <= 0) {
-      sk = 1;
-    }
-  }
-  TORCH_CHECK(cfg < gemm_w4a8_num_configs(), "unknown MXFP4 GEMM config ", cfg);
-  sk = std::min(sk, gemm_w4a8_max_splitk(cfg, (int)K));
-  at::Tensor ws;
-  if (sk > 1) {
-    const int64_t need = (int64_t)gemm_w4a8_workspace_bytes((int)M, (int)N, sk) / 4;
-    if (workspace.has_value()) {
-      ws = *workspace;
-      TORCH_CHECK(ws.is_cuda() && ws.device() == a.device() && ws.scalar_type() == at::kFloat &&
-                      ws.is_contiguous() && ws.numel() >= need,
-                  "workspace must be a contiguous fp32 GPU tensor of >= ", need, " elements");
-    } else {
-      ws = at::empty({need}, a.options().dtype(at::kFloat));
-    }
-  }
+  const QuantGemmCommon q =
+      quant_gemm_common(kQuantW4A8, a, M, N, K, bias, residual, act, out, config, splitk, workspace);
+  if (M == 0 || N == 0) return q.c;
   GemmW4A8Args g{a.data_ptr(), (int)a.stride(0), xscale.data_ptr<float>(), wq.data_ptr(), (int)wq.stride(0),
-                 ws_in.data_ptr(), (int)ws_in.stride(0), c.data_ptr(), (int)c.stride(0), bptr, rptr, ldr, (int)M, (int)N, (int)K,
-                 (int)act, (float)alpha, cfg, sk, sk > 1 ? ws.data_ptr<float>() : nullptr, (int)store_pol};
+                 ws_in.data_ptr(), (int)ws_in.stride(0), q.c.data_ptr(), (int)q.c.stride(0), q.bias, q.R, q.ldr, (int)M,
+                 (int)N, (int)K, (int)act, (float)alpha, q.cfg, q.sk, q.workspace, (int)store_pol};
   launch_gemm_w4a8(g, cur_stream());
-  return c;
+  return q.c;
 }
 
 // (q, scale) outputs of the row quantisers: e4m3 [M][K] contiguous rows and fp32 [M], the

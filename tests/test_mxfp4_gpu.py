@@ -195,6 +195,23 @@ def test_swiglu_interleaved_rows(N):
         _close(out, want)
 
 
+@pytest.mark.parametrize("M,N,K,col0", [(77, 130, 224, 8), (77, 130, 224, 3), (200, 48, 832, 8), (1, 64, 64, 5)])
+def test_no_stray_writes(M, N, K, col0):
+    """``out`` is a view inside a larger buffer of sentinels: nothing outside it changes (row
+    and column tails, K no multiple of a slice; 8-byte aligned and unaligned views: vector and
+    scalar stores)."""
+    xq, xs, q, s, ref = _problem(M, N, K, seed=8)
+    sentinel = 1000.0  # a bf16 value
+    for cfg in [None] + _configs():
+        big = torch.full((M + 5, N + 22), sentinel, dtype=torch.bfloat16, device=DEV)
+        out = big[2:2 + M, col0:col0 + N]
+        ops.linear_w4a8(xq, xs, q, s, out=out, config=cfg)
+        _close(out, ref)
+        mask = torch.ones_like(big, dtype=torch.bool)
+        mask[2:2 + M, col0:col0 + N] = False
+        assert (big[mask] == sentinel).all(), f"config {cfg}"
+
+
 def test_two_runs_are_bitwise_equal():
     xq, xs, q, s, ref = _problem(200, 208, 1024, seed=9)
     bias, res = _rand(208, seed=10), _rand(200, 208, seed=11)
