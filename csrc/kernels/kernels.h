@@ -349,6 +349,28 @@ void launch_decode_prologue(const int* pos, const int* tokens, int* tok_out, con
                             int row_bytes0, const void* tab1, void* out1, int row_bytes1, int B, int T, int C,
                             hipStream_t s);
 
+// Chunk attention over the cache (attn_chunk.hip): T queries per sequence, 1 <= T <= 1024, query
+// row b*T + t against cache rows 0 .. min(pos[b]+t, C-1) of sequence b; rows at or past pos[b]+T
+// are never read. bf16 caches only (fp8 ones go through launch_kv_dequantize_rows first).
+struct ChunkAttnArgs {
+  const void* q; int ldq;  // bf16 [B*T][>= n_head*D]
+  const void* k_cache;     // bf16 [B][C][n_kv_head*D]
+  const void* v_cache;
+  void* o; int ldo;        // bf16 [B*T][>= n_head*D]
+  const int* pos;          // int32 [B], read by the kernel
+  int B, T, C, n_head, n_kv_head, D;
+  float scale;
+  int variant = 0;         // 0: by block count; 2, 8, 13: that configuration of attention.hip
+};
+bool attn_chunk_supported(int T, int n_head, int n_kv_head, int D);
+int attn_chunk_variant(int B, int T, int n_head, int variant);  // the configuration a launch takes
+void launch_attn_chunk(const ChunkAttnArgs& a, hipStream_t s);
+// out[b][r] = e4m3 cache[b][r] x scale[b][h][r] as bf16 for r < min(pos[b]+T, C); no other row is written
+void launch_kv_dequantize_rows(const void* cache, const float* scale, const int* pos, void* out, int B, int T, int C,
+                               int n_kv_head, int D, hipStream_t s);
+// pos[b] = min(pos[b] + T, max(limit[b], pos[b]))
+void launch_kv_advance(int* pos, const int* limit, int B, int T, hipStream_t s);
+
 // Token sampling over the last logits row of every sequence (sample.hip): greedy, temperature,
 // top-k and top-p by whole value classes, a Philox4x32-10 draw in index order, and the stream
 // rule that feeds the token back into tokens[b][pos[b]+T]. One launch; a row is split over

@@ -44,6 +44,19 @@ const bool kSplitKFixup = [] {
   const char* e = std::getenv("DLS_SPLITK_FIXUP");
   return !(e && e[0] == '0');
 }();
+// Most K slices a split-K GEMM may still combine in its own launch. The in-launch combine adds the
+// other slices to the LAST ARRIVER's accumulators, so from three slices on the order of the sum
+// follows the arrival order and the result differs from run to run in the last bits; the reduce
+// kernel sums the slabs in slice order. A caller that needs bit-identical repeats sets 2 (a sum of
+// two terms has one order). Read at launch time on the host: a captured launch keeps its choice.
+// Per host thread: executors that issue steps from different threads of one process (loopback
+// ranks, replica ranks) do not see each other's value.
+thread_local int g_fixup_max_slices = 1 << 30;
+int64_t gemm_fixup_max_slices(int64_t n) {
+  const int old = g_fixup_max_slices;
+  if (n > 0) g_fixup_max_slices = (int)std::min<int64_t>(n, 1 << 30);
+  return old;
+}
 
 void check_bf16(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
@@ -237,7 +250,7 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
   if (sk > 1) {
     ws = at::empty({(int64_t)gemm_glds_workspace_bytes((int)M, (int)N, sk) / 4}, a.options().dtype(at::kFloat));
     // (a post-norm wants the row-owning reduce kernel, not the in-launch combine)
-    if (kSplitKFixup && !rowp && !norm_out.has_value()) {
+    if (kSplitKFixup && sk <= g_fixup_max_slices && !rowp && !norm_out.has_value()) {
       // one counter per output tile of the config the launcher resolves to (sk > 1: no in-kernel
       // row statistics here)
       int bm, bn;
@@ -659,6 +672,74 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& k_cache, cons
   a.part = part.data_ptr(), a.cnt = cnt.data_ptr();
   launch_attn_decode(a, cur_stream());
   return o;
+}
+
+// ---- chunk attention over the cache (attn_chunk.hip)
+
+// rows 0 .. min(pos[b]+T, C)-1 of an e4m3 cache times their scales into a bf16 buffer of its shape
+void kv_dequantize_rows(const at::Tensor& cache, const at::Tensor& scale, const at::Tensor& pos, int64_t T,
+                        const at::Tensor& out) {
+  TORCH_CHECK(cache.dim() == 3 && cache.is_cuda() && cache.scalar_type() == at::kByte && cache.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(cache.data_ptr()) % 16 == 0,
+              "kv_dequantize_rows: the cache must be a contiguous uint8 GPU tensor [B][C][n_kv_head*head_dim]");
+  const int64_t B = cache.size(0), C = cache.size(1), E = cache.size(2);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.dim() == 3 &&
+                  scale.size(0) == B && scale.size(2) == C && scale.size(1) >= 1 && E % scale.size(1) == 0,
+              "kv_dequantize_rows: scales must be contiguous fp32 GPU tensors [B][n_kv_head][C]");
+  const int64_t H = scale.size(1), D = E / H;
+  TORCH_CHECK(D % 8 == 0 && T >= 1 && B >= 1 && B <= 65535 && C >= 1 && C * E / 8 < (1ll << 31),
+              "kv_dequantize_rows: head_dim must be a multiple of 8, T >= 1, B <= 65535");
+  check_bf16(out, "out");
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == cache.sizes() &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "kv_dequantize_rows: out must be a contiguous 16-byte aligned bf16 tensor of the cache's shape");
+  check_i32(pos, B, "pos");
+  launch_kv_dequantize_rows(cache.data_ptr(), scale.data_ptr<float>(), pos.data_ptr<int>(), out.data_ptr(), (int)B,
+                            (int)T, (int)C, (int)H, (int)D, cur_stream());
+}
+
+int64_t attention_chunk_variant(int64_t B, int64_t T, int64_t n_head, int64_t variant) {
+  return attn_chunk_variant((int)B, (int)T, (int)n_head, (int)variant);
+}
+
+at::Tensor attention_chunk(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                           const at::Tensor& pos, int64_t T, int64_t n_head, int64_t n_kv_head, int64_t head_dim,
+                           double scale, const c10::optional<at::Tensor>& out, int64_t variant) {
+  TORCH_CHECK(k_cache.dim() == 3, "caches must be [B][C][n_kv_head*head_dim]");
+  const int64_t B = k_cache.size(0), C = k_cache.size(1);
+  TORCH_CHECK(n_kv_head >= 1 && attn_chunk_supported((int)T, (int)n_head, (int)n_kv_head, (int)head_dim),
+              "attention_chunk: needs 1 <= T <= 1024, n_head a multiple of n_kv_head and head_dim 64 or 128 (T ", T,
+              ", heads ", n_head, "/", n_kv_head, ", head_dim ", head_dim, ")");
+  TORCH_CHECK(variant == 0 || variant == 2 || variant == 8 || variant == 13,
+              "attention_chunk: variant must be 0, 2, 8 or 13");
+  TORCH_CHECK(B >= 1 && B <= 65535 && n_head <= 65535 && C >= 1, "attention_chunk: batch / capacity");
+  TORCH_CHECK(!check_caches(k_cache, v_cache, n_kv_head * head_dim, c10::nullopt, c10::nullopt, n_kv_head),
+              "attention_chunk: the kernel takes bf16 caches");
+  check_bf16(q, "q");
+  check_rows(q, "q");
+  TORCH_CHECK(q.size(0) == B * T && q.size(1) >= n_head * head_dim, "q must be [B*T][>= n_head*head_dim]");
+  check_i32(pos, B, "pos");
+  at::Tensor o = out.has_value() ? as2d(*out) : at::empty({B * T, n_head * head_dim}, q.options());
+  check_bf16(o, "out");
+  check_rows(o, "out");
+  TORCH_CHECK(o.size(0) == B * T && o.size(1) >= n_head * head_dim, "out must be [B*T][>= n_head*head_dim]");
+  ChunkAttnArgs a{};
+  a.q = q.data_ptr(), a.ldq = (int)q.stride(0);
+  a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr();
+  a.o = o.data_ptr(), a.ldo = (int)o.stride(0);
+  a.pos = pos.data_ptr<int>();
+  a.B = (int)B, a.T = (int)T, a.C = (int)C, a.n_head = (int)n_head, a.n_kv_head = (int)n_kv_head;
+  a.D = (int)head_dim, a.scale = (float)scale, a.variant = (int)variant;
+  launch_attn_chunk(a, cur_stream());
+  return o;
+}
+
+void kv_advance(const at::Tensor& pos, const at::Tensor& limit, int64_t T) {
+  const int64_t B = pos.numel();
+  TORCH_CHECK(B >= 1 && T >= 0 && T < (1 << 30), "kv_advance: B >= 1, 0 <= T < 2^30");
+  check_i32(pos, B, "pos");
+  check_i32(limit, B, "limit");
+  launch_kv_advance(pos.data_ptr<int>(), limit.data_ptr<int>(), (int)B, (int)T, cur_stream());
 }
 
 // one launch per step: the step's token ids and its rows of up to two [C][*] position tables
@@ -1616,6 +1697,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("scale"),
         py::arg("part"), py::arg("cnt"), py::arg("out") = py::none(), py::arg("chunk") = 0,
         py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("gemm_fixup_max_slices", &gemm_fixup_max_slices, py::arg("n") = 0);
+  m.def("kv_dequantize_rows", &kv_dequantize_rows, py::arg("cache"), py::arg("scale"), py::arg("pos"), py::arg("T"),
+        py::arg("out"));
+  m.def("attention_chunk_variant", &attention_chunk_variant, py::arg("B"), py::arg("T"), py::arg("n_head"),
+        py::arg("variant") = 0);
+  m.def("attention_chunk", &attention_chunk, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("pos"),
+        py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("scale"),
+        py::arg("out") = py::none(), py::arg("variant") = 0);
+  m.def("kv_advance", &kv_advance, py::arg("pos"), py::arg("limit"), py::arg("T"));
   m.def("decode_prologue", &decode_prologue, py::arg("pos"), py::arg("tokens"), py::arg("tok_out"), py::arg("T"),
         py::arg("C"), py::arg("tables"), py::arg("outs"));
   m.def("sample_sizes", &sample_sizes_b, py::arg("B"), py::arg("V"));

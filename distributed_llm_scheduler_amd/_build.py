@@ -174,6 +174,7 @@ def _build_ops(kern, hdrs, hosts, host_hdrs, force, verbose, jobs) -> str:
     # math every tile, so it takes the VGPR form of the MFMAs (no accvgpr read/write shuffles);
     # the GEMMs keep the default (their accumulators only meet the VALU in the epilogue)
     per_file = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                "attn_chunk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_decode_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 

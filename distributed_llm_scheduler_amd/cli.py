@@ -17,7 +17,9 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
   models    list the model presets
   generate  generate tokens from synthetic prompts on one device: a decode plan whose step ends in
             the sampling launch (``runtime.plan(generate=True)``); prints one JSON line with the
-            token ids, the steps and the tokens per second
+            token ids, the steps and the tokens per second. ``--prefill-chunk Tc``: the prompts are
+            consumed in chunk steps of Tc tokens per sequence (``runtime.plan(prefill_chunk=Tc)``); the
+            line then also gives the chunk-step count and the time to the first generated token
 
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
@@ -380,7 +382,7 @@ def cmd_generate(a) -> int:
     if a.prompt_len < 1 or a.new < 1 or a.prompt_len + a.new > a.kv_cache:
         raise SystemExit(f"--prompt-len {a.prompt_len} + --new {a.new} must be positive and fit --kv-cache {a.kv_cache}")
     p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
-                     kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True)
+                     kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk)
     store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
     prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
@@ -388,17 +390,28 @@ def cmd_generate(a) -> int:
     ex.set_prompts("@tokens", prompts)
     ex.step()  # (derives weights, tunes nothing new afterwards)
     captured = ex.capture() if gpu and not a.no_graph else False
+    first = {}
+    if a.prefill_chunk is not None:
+        # time to the first generated token: the chunk steps of the prompt plus one token step
+        ex.set_prompts("@tokens", prompts)
+        if gpu:
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ex.generate(1)
+        first = {"prefill_chunk": a.prefill_chunk, "chunk_steps": ex.prefill_steps,
+                 "first_token_ms": round((time.perf_counter() - t0) * 1e3, 4)}
     ex.set_prompts("@tokens", prompts)
     if gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     tokens = ex.generate(a.new)
     dt = time.perf_counter() - t0
-    steps = a.prompt_len - 1 + a.new
+    steps = a.prompt_len - 1 + a.new if a.prefill_chunk is None else ex.prefill_steps + a.new
     print(json.dumps({"model": a.model, "device": str(dev), "batch": a.batch, "kv_cache": a.kv_cache,
                       "kv_dtype": a.kv_dtype, "prompt_len": a.prompt_len, "new": a.new, "temperature": a.temperature,
                       "top_k": a.top_k, "top_p": a.top_p, "seed": a.seed, "graph": bool(captured), "steps": steps,
-                      "step_ms": round(dt / steps * 1e3, 4), "tokens_per_s": round(a.batch * steps / dt, 2),
+                      "step_ms": round(dt / steps * 1e3, 4),
+                      "tokens_per_s": round(a.batch * (a.prompt_len - 1 + a.new) / dt, 2), **first,
                       "prompts": prompts, "tokens": tokens}))
     return 0
 
@@ -474,6 +487,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--hbm-cap-gb", type=float, default=288.0)
     g.add_argument("--device", default="auto", choices=["auto", "cpu"])
     g.add_argument("--no-graph", action="store_true")
+    g.add_argument("--prefill-chunk", type=int, default=None, metavar="Tc",
+                   help="consume the prompts in chunk steps of Tc tokens per sequence (2 .. min(C, 1024))")
     g.set_defaults(fn=cmd_generate)
     a = ap.parse_args(argv)
     return a.fn(a)

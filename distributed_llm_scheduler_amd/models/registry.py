@@ -140,6 +140,26 @@ def check_generate(generate: bool, seq: int, kv_cache: "int | None") -> None:
                          "whose tokens are not generated yet")
 
 
+PREFILL_MAX_CHUNK = 1024  # widest query chunk of ops.attention_chunk
+
+
+def check_prefill_chunk(prefill_chunk, seq: int, kv_cache: "int | None") -> None:
+    """What chunked prompt prefill (``prefill_chunk=Tc``: a second step shape of Tc tokens per
+    sequence next to the token step) needs of a plan; works with or without ``generate`` and with
+    either ``kv_dtype``."""
+    if prefill_chunk is None:
+        return
+    if kv_cache is None:
+        raise ValueError("prefill_chunk needs a KV cache (kv_cache=C): a chunk step fills the caches of decode steps")
+    if seq != 1:
+        raise ValueError(f"prefill_chunk needs seq=1, got {seq}: the plan's own step is the token step, the chunk "
+                         "step is its second shape")
+    hi = min(kv_cache, PREFILL_MAX_CHUNK) if isinstance(kv_cache, int) else PREFILL_MAX_CHUNK  # (kv_cache: checked by build)
+    if not isinstance(prefill_chunk, int) or isinstance(prefill_chunk, bool) or not 2 <= prefill_chunk <= hi:
+        raise ValueError(f"prefill_chunk must be an int in 2 .. min(kv_cache, {PREFILL_MAX_CHUNK}) = {hi}, "
+                         f"got {prefill_chunk!r}")
+
+
 def sample_slices(B: int, V: int):
     """(workgroups per row, elements per workgroup) of the sampling kernel (csrc/kernels/sample.hip
     ``sample_slices``), for its workspace's bytes."""

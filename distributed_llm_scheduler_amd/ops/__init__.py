@@ -816,6 +816,104 @@ def attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, s
     return y
 
 
+# ---------------------------------------------------------- prompt chunks over the cache
+CHUNK_MAX_T = 1024  # widest query chunk of attention_chunk
+CHUNK_VARIANTS = (2, 8, 13)  # the (NW, ST, KS) configurations its launcher chooses among, by ops.attention's numbers
+
+
+def kv_dequantize_rows(cache, scale, pos, T, out):
+    """Rows ``0 .. min(pos[b]+T, C)-1`` of every sequence of an fp8 cache (uint8 e4m3 [B][C][E], scales
+    fp32 [B][n_kv_head][C]) into ``out`` (bf16 [B][C][E]) as e4m3 x scale, each value exactly a bf16:
+    :func:`kv_dequantize` on those rows, and no other row of ``out`` is touched. One launch on the
+    GPU (attn_chunk.hip), ``pos`` read on the device."""
+    if cache.dtype != torch.uint8 or cache.dim() != 3:
+        raise RuntimeError("kv_dequantize_rows: the cache must be uint8 (e4m3) [B][C][n_kv_head*head_dim]")
+    B, C, E = cache.shape
+    if scale.dtype != torch.float32 or scale.dim() != 3 or scale.shape[0] != B or scale.shape[2] != C \
+            or scale.shape[1] < 1 or E % scale.shape[1] or (E // scale.shape[1]) % 8:
+        raise RuntimeError("kv_dequantize_rows: scales must be fp32 [B][n_kv_head][C], head_dim a multiple of 8")
+    if out.dtype != torch.bfloat16 or out.shape != cache.shape or not out.is_contiguous() or T < 1:
+        raise RuntimeError("kv_dequantize_rows: out must be contiguous bf16 of the cache's shape, T >= 1")
+    if _gpu(cache):
+        ext().kv_dequantize_rows(cache, scale, pos, int(T), out)
+        return out
+    for b, p in enumerate(pos.tolist()):
+        n = min(max(min(p, C), 0) + T, C)
+        out[b, :n] = kv_dequantize(cache[b:b + 1, :n], scale[b:b + 1, :, :n])[0]
+    return out
+
+
+def attention_chunk_variant(B, T, n_head, variant=0):
+    """The configuration (one of ``CHUNK_VARIANTS``) the GPU launcher of ``attention_chunk`` takes."""
+    return ext().attention_chunk_variant(int(B), int(T), int(n_head), int(variant))
+
+
+def attention_chunk(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None, out=None,
+                    k_scale=None, v_scale=None, workspace=None, variant=0):
+    """Causal attention of a prompt chunk: the ``T`` queries of every sequence (q [B*T][>=
+    n_head*head_dim], 1 <= T <= 1024, any n_head / n_kv_head) against its cache rows; query row
+    ``b*T + t`` attends rows ``0 .. min(pos[b]+t, C-1)``. Runs after ``kv_append``, as
+    ``attention_decode`` does. ``pos`` (int32 [B]) is read on the device and the grid depends on
+    (T, n_head, B) alone, so a captured launch follows a growing, ragged batch. Cache rows at or past
+    ``pos[b]+T`` are never read; rows of query positions >= C are unspecified but finite.
+    Cache rows below ``pos[b]+T`` must hold finite V values, also those a query does not see
+    (``pos[b]+t < r < pos[b]+T``, written by the step's own append): a row of a loaded tile that the
+    causal mask hides enters the product with V as ``0 x v`` on both paths, as in ``attention``.
+    A hidden K row may hold anything: its score is replaced by the mask.
+    GPU: attn_chunk.hip (``variant``: 0 = chosen by block count, or one of ``CHUNK_VARIANTS``).
+    With ``k_scale`` / ``v_scale`` the caches are fp8: ``kv_dequantize_rows`` fills ``workspace`` —
+    two bf16 [B][C][n_kv_head*head_dim] buffers (K, V) allocated by the caller — and the bf16 kernel
+    runs on it. CPU: fp32 torch."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
+    if k_cache.dim() != 3:
+        raise RuntimeError("attention_chunk: caches must be [B][C][n_kv_head*head_dim]")
+    if not (1 <= T <= CHUNK_MAX_T and n_kv_head >= 1 and n_head % n_kv_head == 0):
+        raise RuntimeError("attention_chunk: needs 1 <= T <= 1024 and n_head a multiple of n_kv_head "
+                           f"(T {T}, heads {n_head}/{n_kv_head})")
+    if variant not in (0,) + CHUNK_VARIANTS:
+        raise RuntimeError(f"attention_chunk: variant must be 0 or one of {CHUNK_VARIANTS}")
+    fp8 = _kv_scales_ok(k_cache, v_cache, k_scale, v_scale, "attention_chunk")
+    if fp8:
+        if k_scale.shape[1] != n_kv_head:
+            raise RuntimeError("attention_chunk: scales must be fp32 [B][n_kv_head][C]")
+        if _gpu(q):
+            if workspace is None or len(workspace) != 2:
+                raise ValueError("attention_chunk with fp8 caches needs workspace=(k, v): two bf16 buffers of the "
+                                 "caches' shape")
+            k_cache = kv_dequantize_rows(k_cache, k_scale, pos, T, workspace[0])
+            v_cache = kv_dequantize_rows(v_cache, v_scale, pos, T, workspace[1])
+        else:
+            k_cache, v_cache = kv_dequantize(k_cache, k_scale), kv_dequantize(v_cache, v_scale)
+    if _gpu(q):
+        return ext().attention_chunk(q, k_cache, v_cache, pos, int(T), n_head, n_kv_head, head_dim, float(scale), out,
+                                     int(variant))
+    y = ref_attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale)
+    if out is not None:
+        out[:, :n_head * head_dim].copy_(y)
+        return out
+    return y
+
+
+def kv_advance(pos, limit, T, tmp=None):
+    """``pos[b] = min(pos[b] + T, max(limit[b], pos[b]))`` in place (int32 [B] each): a chunk step's
+    advance, which stops every sequence at its target and never moves one back. One tiny launch
+    on the GPU. CPU: three in-place torch ops through ``tmp`` (int32 [B], the caller's), which
+    allocate nothing; without ``tmp`` one such buffer is allocated."""
+    if pos.dtype != torch.int32 or limit.dtype != torch.int32 or pos.shape != limit.shape or pos.dim() != 1 \
+            or not 0 <= T < 1 << 30:
+        raise RuntimeError("kv_advance: pos and limit must be int32 [B], 0 <= T < 2^30")
+    if _gpu(pos):
+        ext().kv_advance(pos, limit, int(T))
+        return
+    if tmp is None:
+        tmp = torch.empty_like(pos)
+    elif tmp.dtype != torch.int32 or tmp.shape != pos.shape:
+        raise RuntimeError("kv_advance: tmp must be int32 [B]")
+    torch.maximum(limit, pos, out=tmp)
+    pos.add_(int(T))
+    torch.minimum(pos, tmp, out=pos)
+
+
 def decode_prologue(pos, T, C, tokens=None, tok_out=None, tables=(), outs=()):
     """One launch per step: ``tok_out[b*T + t] = tokens[b][p]`` and ``outs[i][b*T + t] =
     tables[i][p]`` at ``p = min(pos[b] + t, C - 1)``. ``tokens`` int32 [B][C]; ``tables`` up to

@@ -44,7 +44,7 @@ from ..models.params import ParamStore, group_layout, quant_parts
 from ..utils.tracing import Roctx
 from . import lifetime
 from .comm import make_comm
-from .program import Program
+from .program import Program, group_workspace_bytes, plan_prefill
 
 
 @dataclass
@@ -191,8 +191,16 @@ class DAGExecutor:
                  model_cfg=None, use_graph: bool = True, pg=None, seed: int = 1234, autotune: bool = True,
                  trace: bool = False, debug: bool = False, model_name: Optional[str] = None,
                  input_parts: Optional[Dict[str, List[str]]] = None,
-                 requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16"):
+                 requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16",
+                 prefill_chunk: Optional[int] = None):
         self.tasks = {t.id: t for t in tasks}
+        # runtime.plan prefill_chunk=Tc: the program also runs as a chunk step of Tc tokens per sequence
+        self.prefill_chunk = int(prefill_chunk) if prefill_chunk else None
+        self._chunk_on = False  # a chunk step is being issued (_chunk_mode)
+        self._ck: Optional[dict] = None  # the chunk shape's views and buffers (_setup_prefill)
+        self._chunk_graph = self._chunk_exec = None
+        self.chunk_launches: Optional[int] = None  # kernel launches of one captured chunk step
+        self.prefill_steps: Optional[int] = None   # chunk steps of the last generate()
         # the model whose per-model GEMM choices (ops/gemm_tuning.json model_overrides) this
         # executor's launches use: set around each of its steps, captures and refinements, so
         # executors of different models in one process do not change each other's choices
@@ -325,6 +333,9 @@ class DAGExecutor:
         for ins in p.instrs:
             if ins.op == "run":
                 ws = max(ws, self._workspace_bytes(ins))
+        # (one slab for both step shapes: the chunk step's groups need Tc times the rows)
+        self._pp = plan_prefill(self.tasks, p, self.prefill_chunk) if self.prefill_chunk else None
+        ws = max(ws, 256) + (self._pp.ws_extra if self._pp is not None else 0)
         self._ws_full = torch.empty(max(ws, 256) + g, dtype=torch.uint8, device=dev)
         self.ws_slab = self._ws_full[:self._ws_full.numel() - g]
         if g:
@@ -388,6 +399,7 @@ class DAGExecutor:
             self._plan_post_norm()  # (pairs are adjacent runs: no p2p between producer and consumer)
         self._plan_mlp_fused()
         self._setup_kv()
+        self._setup_prefill()
 
     def _plan_post_norm(self) -> None:
         """Pair each norm that the next group would run as its own pass (its width is above
@@ -846,6 +858,16 @@ class DAGExecutor:
                 # at K = 4096 the separate norm kernel is cheaper than the split-K reduce
                 # epilogue work (Llama-3-8B 9.89 vs 9.96 ms)
                 width = self.tasks[src].op.out_shape[-1] if src in self.tasks else 0
+                # A plan with prefill_chunk promises bit-identical repeats of a generation. A producer
+                # adds its tiles' (and its reduce kernel's lanes') partial sums with float atomics in
+                # arrival order, so handed-over statistics differ from run to run in the last bits
+                # (measured: profiles/prefill_chunk/determinism.txt). Both step shapes of such a plan
+                # therefore keep the hand-off only where it decides whether the norm is folded into
+                # the consumer's weight (width > FOLD_MAX_K, i.e. DLS_HANDOFF_MAX_K raised); up to
+                # FOLD_MAX_K the norm is folded either way and the consumer GEMM accumulates the
+                # statistics in its main loop: the same launches, no unordered sum.
+                if self.prefill_chunk and width <= FOLD_MAX_K:
+                    continue
                 if pi is not None and emits(pi) and src not in need and width <= HANDOFF_MAX_K:
                     need.append(src)
         if not need:
@@ -870,14 +892,18 @@ class DAGExecutor:
                 continue
             for t in (self.tasks[x] for x in ins.group):
                 shapes |= self._gemm_shapes_of(t)
+        if self._pp is not None:  # the chunk step's GEMMs: the same weights at Tc times the rows
+            for i in self._pp.runs:
+                for t in (self.tasks[x] for x in self.prog.instrs[i].group):
+                    shapes |= self._gemm_shapes_of(t, self._pp.Tc)
         return sorted(shapes)
 
-    def _gemm_shapes_of(self, t):
+    def _gemm_shapes_of(self, t, rows_mult: int = 1):
         """(M, N, K, variant) of the GEMMs task ``t`` launches (see ops.tuning.tag)."""
         shapes = set()
         op = t.op
         if op is not None and op.out_shape:
-            M = math.prod(op.out_shape[:-1])
+            M = math.prod(op.out_shape[:-1]) * rows_mult
             g = self.store.groups
             spec = {s.name: s for pid in t.params_needed for s in g[pid].tensors}
             names = [(k, v) for k, v in op.weights.items() if k.startswith("w") and isinstance(v, str)]
@@ -898,29 +924,7 @@ class DAGExecutor:
         return shapes
 
     def _workspace_bytes(self, ins) -> int:
-        grp = [self.tasks[x] for x in ins.group]
-        t = grp[1] if len(grp) > 1 and grp[0].op is not None and grp[0].op.kind in ("layernorm", "rmsnorm") \
-            else grp[0]
-        if t.op is None:
-            return 0
-        k = t.op.kind
-        M = math.prod(t.op.out_shape[:-1]) if t.op.out_shape else 0
-        a = t.op.attrs
-        if k == "attention":
-            D = a["head_dim"]
-            qkv = M * (a["n_head"] + 2 * a["n_kv_head"]) * D
-            return 2 * (qkv + M * a["n_head"] * D) + 512
-        if k == "swiglu_mlp":
-            F = a["ffn"]
-            return 2 * (M * 2 * F + M * F) + 512
-        if k == "attn_sp":
-            # gathered K/V of the visible chunks + the attention output
-            D = a["head_dim"]
-            keys = M * len(t.op.inputs)
-            return 2 * (keys * 2 * a["n_kv_head"] * D + M * a["n_head"] * D) + 1024
-        if k == "moe":
-            return 0
-        return 0
+        return group_workspace_bytes(self.tasks, ins)
 
     def _ws(self, offset_elems: int, shape) -> torch.Tensor:
         n = math.prod(shape)
@@ -1558,6 +1562,8 @@ class DAGExecutor:
         for st in self._kv_first.get(i, ()):
             self._kv_prologue(st)
         self._run_group_body(ins)
+        if self._chunk_on:
+            return  # a chunk step advances every pos once, at its end (_chunk_body)
         for st in self._kv_last.get(i, ()):
             st["pos"].add_(st["T"])
 
@@ -1585,7 +1591,7 @@ class DAGExecutor:
             wpe = self._w(W["wpe"]) if "wpe" in W else None
             st = self._kv.get(_kv_prefix(head.id)) if self._kv else None
             if st is not None:  # decode step: the tokens and wpe rows gathered at pos, one row each
-                tok, wpe, S = st["tok_g"], st["wpe_g"], B * S
+                tok, wpe, S = st["tok_g"], st["wpe_g"], B * st["T"]  # (T: the step shape's, Tc in a chunk step)
             if "seq_chunk" in a:  # sequence chunk c: its token slice, positions from c*S on
                 c, P = a["seq_chunk"]
                 tok = tok.view(B, S * P)[:, c * S:(c + 1) * S]
@@ -1633,6 +1639,7 @@ class DAGExecutor:
                 # decode step: QKV of the T new tokens (RoPE from the table rows gathered at pos:
                 # with S = M the kernels' row % S is the row), append, attend the caches, project
                 st = self._kv[_kv_prefix(head.id)]
+                S = st["T"]  # the step shape's tokens per sequence: out_shape[1], or Tc in a chunk step
                 kc, vc, *sc = self._kv_cache[head.id]
                 ks, vs = sc if sc else (None, None)  # kv_dtype="fp8": the scales of the byte caches
                 if a.get("rope"):
@@ -1641,8 +1648,15 @@ class DAGExecutor:
                 else:
                     self._gemm(x, W["w_qkv"], W.get("b_qkv"), norm, out=qkv)
                 ops.kv_append(qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], kc, vc, st["pos"], S, ks, vs)
-                ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, workspace=self._kv_ws,
-                                     k_scale=ks, v_scale=vs)
+                if self._chunk_on:
+                    f8 = None
+                    if ks is not None and self.gpu:  # the rank's one bf16 workspace, viewed as this layer's caches
+                        f8 = tuple(w[:kc.numel()].view(kc.shape) for w in self._ck["f8"])
+                    ops.attention_chunk(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, k_scale=ks,
+                                        v_scale=vs, workspace=f8)
+                else:
+                    ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o,
+                                         workspace=self._kv_ws, k_scale=ks, v_scale=vs)
                 self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
                              post_norm=self._post_norm_out(self._flat(out)))
                 return
@@ -1765,7 +1779,7 @@ class DAGExecutor:
             for k in hoist[-1]:
                 if k not in pending:
                     self._prefetch(k, ev0, stats, pending, events)
-        segs = self._segments if (events is None and not tr) else {}
+        segs = self._segments if (events is None and not tr and not self._chunk_on) else {}
         pulls = sorted(self._pull_at)
         n_ins = len(self.prog.instrs)
         i = -1
@@ -2096,8 +2110,12 @@ class DAGExecutor:
         self._wait_sends(ins)  # output region about to be overwritten: its sends must be done
 
     def _issue_run(self, i: int, ins, stats: StepStats, events) -> None:
+        if self._chunk_on and i not in self._ck["runs"]:
+            return  # a chunk step runs the groups up to the last attention only
         given = self._norm_given.get(i)
         self._pn, self._pn_given = self._post_norm.get(i), (given if given == self._pn_done else None)
+        if self._chunk_on and self._pn is not None and self._pn.id not in self._ck["norms"]:
+            self._pn = None  # the norm's consumer is not part of the chunk step
         if given is not None:
             self._pn_done = None
         try:
@@ -2311,7 +2329,7 @@ class DAGExecutor:
             raise RuntimeError(f"rank {self.prog.rank}: fused MLP block gave up waiting for fc1 tiles "
                                f"(error word {int(self._mlp_sync[-1].item())}); this step's outputs are wrong")
 
-    def check_guards(self) -> None:
+    def check_guards(self, chunk: bool = False) -> None:
         """Debug mode: every arena's trailing canary is intact and the rank's outputs are
         finite (a kernel writing past its planned region or producing NaN fails loudly)."""
         if self.gpu:
@@ -2319,10 +2337,18 @@ class DAGExecutor:
         slabs = [("activation", self._act_full), ("parameter", self._param_full), ("workspace", self._ws_full)]
         if self._kv_full is not None:
             slabs.append(("KV cache", self._kv_full))
+        if self._prefill_full is not None:
+            slabs.append(("prefill", self._prefill_full))
         for name, full in slabs:
             tail = full[-GUARD_BYTES:]
             if not bool((tail == GUARD_VALUE).all()):
                 raise RuntimeError(f"rank {self.prog.rank}: {name} arena guard overwritten (out-of-bounds write)")
+        if chunk:  # after a chunk step: its last group's rows (dead rows included), not the token step's outputs
+            if self._ck is not None:
+                tid = self.prog.instrs[max(self._ck["runs"])].task
+                if not bool(torch.isfinite(self._ck["views"][tid].float()).all()):
+                    raise RuntimeError(f"rank {self.prog.rank}: non-finite values in the chunk step's output of {tid}")
+            return
         for ins in self.prog.instrs:
             if ins.op == "run" and not self._consumed_locally(ins.task):
                 v = self._views[ins.task]
@@ -2348,7 +2374,8 @@ class DAGExecutor:
         program without copy-stream refills, else its kernel-group segments (capture_segments).
         With KV caches the steps a capture runs to warm up leave no trace: the positions are put
         back afterwards (the cache rows they wrote lie past them, where every mask hides them and
-        the next step writes again)."""
+        the next step writes again). A plan with ``prefill_chunk`` whose token step is one graph gets
+        its chunk step as a second one (``chunk_launches``)."""
         if not self.use_graph:
             return False
         if not self._kv:
@@ -2360,7 +2387,20 @@ class DAGExecutor:
                 if st["sample"] is not None}
         self._kv_hold = True
         try:
-            return self._capture()
+            if self._ck is not None:
+                # Two step shapes share buffers that grow on demand and free the old one (_scratch,
+                # _a8_rows, _w8_ws): an eager chunk step takes each to its larger size BEFORE either
+                # graph is captured, so no captured pointer is freed later. It also applies every
+                # in-place weight transform (_prep, _prep_w8), whose decisions are the same for both
+                # shapes: they depend on the weight, the norm's width and which groups hand over
+                # row statistics (the chunk step keeps the token step's pairs), never on the rows.
+                self._sync()
+                self._chunk_body(StepStats())
+                self._sync()
+            ok = self._capture()
+            if ok and self._ck is not None and self._graph is not None:
+                self._capture_chunk()
+            return ok
         finally:
             self._kv_hold = False
             self._sync()
@@ -2434,6 +2474,7 @@ class DAGExecutor:
         capture are replaced — hand them to the graveyard (destroyed at a quiesce point; on the
         main thread right away) instead of keeping every capture alive until the executor dies."""
         self._graph = self._graph_exec = None
+        self._chunk_graph = self._chunk_exec = None
         self._segments = {}
         self._drop_runner()
         self._fast = None
@@ -2736,6 +2777,10 @@ class DAGExecutor:
         if self._kv_full is not None:
             m["kv_cache"] = sum(c.numel() * c.element_size() for cs in self._kv_cache.values() for c in cs)
             m["kv_slab"] = self.kv_slab.numel()
+        if self._pp is not None:
+            # what the chunk step adds (== Plan.prefill_bytes[rank]): its slab, and the part of the
+            # workspace slab beyond the token step's
+            m["prefill"] = (self.prefill_slab.numel() if self.prefill_slab is not None else 0) + self._pp.ws_extra
         return m
 
     # ------------------------------------------------------------- KV caches and decode steps
@@ -2885,6 +2930,222 @@ class DAGExecutor:
                                        f"embeds elsewhere; a token is fed back on one GPU only")
                 st["top_p"].fill_(1.0)  # the slab is zero: greedy, no top-k, seed 0, nothing done, no prompt
                 st["eos"].fill_(-1)
+
+    # ------------------------------------------------------------- prompt chunks (plan prefill_chunk=Tc)
+    def _setup_prefill(self) -> None:
+        """State of chunk steps: one more slab, laid out by program.plan_prefill (the plan counts the
+        same bytes: Plan.prefill_bytes), holds the chunk activation arena [B, Tc, ...], the row
+        statistics of the chunk rows, per request the device ``limit`` (int32 [B]: where a prefill
+        stops each sequence) and the gathered tokens / wpe / RoPE rows of B*Tc rows, and the bf16
+        workspace fp8 caches are dequantised into — all allocated here, nothing during a step or
+        a capture. The workspace slab was sized for the larger shape in _setup."""
+        self._prefill_full = self.prefill_slab = None
+        pp = self._pp
+        if pp is None:
+            return
+        if self.kv_capacity is None:
+            raise ValueError("prefill_chunk needs a plan with a KV cache (runtime.plan kv_cache=C)")
+        if self._mlp_fused:
+            raise ValueError("prefill_chunk does not combine with DLS_MLP_FUSED=1: the one-launch MLP block is "
+                             "planned for one step shape")
+        if self.prog.has_comm or self._refills():
+            raise ValueError(f"rank {self.prog.rank}: prefill_chunk needs a program without sends, receives and "
+                             f"steady-state parameter refills")
+        for st in self._kv.values():
+            st["limit"], st["limit_h"] = None, [0] * st["B"]
+        if not pp.fields:
+            return  # no chunk group here: the host lengths are all this rank keeps
+        Tc = pp.Tc
+        al = lambda n: (n + 255) // 256 * 256  # noqa: E731
+        g = GUARD_BYTES if self.debug else 0
+        total = sum(al(f[4]) for f in pp.fields)
+        self._prefill_full = torch.zeros(total + g, dtype=torch.uint8, device=self.device)
+        self.prefill_slab = self._prefill_full[:total]
+        if g:
+            self._prefill_full[-g:].fill_(GUARD_VALUE)
+        off, got, per = 0, {}, {}
+        for key, fld, shape, dtype, nbytes in pp.fields:
+            v = self.prefill_slab[off:off + nbytes].view(getattr(torch, dtype)).view(shape)
+            off += al(nbytes)
+            if key.startswith("@"):
+                got[(key, fld)] = v
+            else:
+                per.setdefault(key, {})[fld] = v
+        arena = got[("@arena", "arena")]
+        views: Dict[str, torch.Tensor] = {}
+        for tid, o in pp.act_offset.items():
+            t = self.tasks[tid]
+            shape = tuple(t.op.out_shape)
+            shape = (shape[0], shape[1] * Tc) + shape[2:]
+            pad = t.op.attrs.get("ld_pad", 1)
+            cols = (shape[-1] + pad - 1) // pad * pad
+            rows = math.prod(shape[:-1])
+            v = arena[o:o + 2 * rows * cols].view(self.dtype).view(rows, cols)
+            if cols != shape[-1]:
+                v = v[:, :shape[-1]]
+            views[tid] = v.view(shape)
+        # the token step's statistics hand-offs whose producer a chunk step runs, in its order (on
+        # such a plan only those that decide a fold, _plan_stats_handoff: the decision transforms
+        # the weight in place and must be the same for both shapes)
+        stats, used, s_out = got[("@stats", "stats")], 0, {}
+        for tid in self._stats_out:
+            if tid in views:
+                n = 2 * math.prod(views[tid].shape[:-1])
+                s_out[tid] = stats[used:used + n]
+                used += n
+        kinds = {}
+        for pre, flds in per.items():
+            st = self._kv[pre]
+            st["limit"] = flds["limit"]
+            kinds[pre] = {f: flds.get(f) for f in ("tok_g", "wpe_g", "cos_g", "sin_g")}
+            kinds[pre]["T"] = st["T"] * Tc
+            if self.gpu:  # prefill() writes limit through pinned memory: no host synchronisation
+                st["limit_pin"] = torch.zeros(st["B"], dtype=torch.int32).pin_memory()
+                st["limit_ev"] = None
+            else:  # the CPU path of kv_advance works through this buffer: no allocation in a step
+                st["adv_tmp"] = torch.zeros(st["B"], dtype=torch.int32)
+        self._ck = dict(runs=set(pp.runs), norms={t for i in pp.runs for t in self.prog.instrs[i].group}, views=views,
+                        stats_out=s_out, ext_stats=dict(s_out), stats_slab=stats[:used] if used else None, st=kinds,
+                        f8=(got[("@f8", "k")], got[("@f8", "v")]) if ("@f8", "k") in got else None)
+
+    def _chunk_need(self) -> None:
+        self._kv_need()
+        if self._pp is None:
+            raise RuntimeError("this plan has no chunk step (runtime.plan prefill_chunk=Tc)")
+
+    def _chunk_body(self, stats: StepStats) -> None:
+        """Issue one chunk step: the program under the chunk shape's views, row statistics and
+        gathered buffers, the groups past the last attention skipped, then one advance per request.
+
+        A sequence with n_b = clamp(limit[b] - pos[b], 0, Tc) < Tc tokens left carries Tc - n_b dead
+        rows. No kernel needs a per-sequence width for them: their K / V rows are appended at
+        pos[b] + n_b .. — at or past the sequence's NEW length pos[b] + n_b, where every later
+        step's mask hides them (a key is visible only below a query's own position) and the next
+        step's append writes again; the live rows t < n_b attend keys <= pos[b] + t only, so no
+        dead row is visible to them; rows at or past C are dropped by kv_append and clamped by the
+        prologue; and the dead rows' own outputs are finite (gathered from real tokens and table
+        rows) and never read as results."""
+        ck = self._ck
+        if ck is None:  # a rank without a chunk group: the program's loads only
+            return
+        saved = (self._views, self._stats_out, self._ext_stats, self._stats_slab)
+        kept = {pre: {f: self._kv[pre][f] for f in flds} for pre, flds in ck["st"].items()}
+        self._views, self._stats_out, self._ext_stats, self._stats_slab = (ck["views"], ck["stats_out"],
+                                                                           ck["ext_stats"], ck["stats_slab"])
+        for pre, flds in ck["st"].items():
+            self._kv[pre].update(flds)
+        self._chunk_on = True
+        # Bit-identical repeats: a split-K GEMM of the chunk shape combines at most two K slices in
+        # its own launch (one order of the sum); wider splits go through the reduce kernel, which
+        # sums in slice order. The in-launch combine otherwise sums from the last-arriving slice
+        # on. A host-side launch choice: the token step keeps its own, and a capture keeps this one.
+        cap = ops.ext().gemm_fixup_max_slices(2) if self.gpu else None
+        try:
+            self._step_body(stats)
+            for pre in ck["st"]:
+                st = self._kv[pre]
+                ops.kv_advance(st["pos"], st["limit"], self._pp.Tc, tmp=st.get("adv_tmp"))
+        finally:
+            if cap is not None:
+                ops.ext().gemm_fixup_max_slices(cap)
+            self._chunk_on = False
+            self._views, self._stats_out, self._ext_stats, self._stats_slab = saved
+            for pre, flds in kept.items():
+                self._kv[pre].update(flds)
+        stats.kernels = len(ck["runs"])
+
+    def step_chunk(self) -> StepStats:
+        """One chunk step (asynchronously on the GPU): every sequence consumes up to Tc tokens of
+        its stream, ``min(Tc, limit - length)`` of them (none once it reached the limit ``prefill``
+        set). A captured chunk step is one graph launch. Call it on every rank alike."""
+        self._chunk_need()
+        Tc = self._pp.Tc
+        if self._chunk_exec is not None:
+            ops.ext().graph_launch(self._chunk_exec, torch.cuda.current_stream(self.device).cuda_stream)
+            stats = StepStats(kernels=len(self._ck["runs"]))
+        else:
+            stats = StepStats()
+            self._chunk_body(stats)
+        # the host lengths follow kv_advance's formula, once the step is issued: a launch that raised
+        # leaves them where the device's pos may still be (kv_reset() brings the two together)
+        for st in self._kv.values():
+            st["len"] = [min(n + Tc, max(lim, n)) for n, lim in zip(st["len"], st["limit_h"])]
+        if self.debug:
+            self.check_guards(chunk=True)
+        self.last = stats
+        return stats
+
+    def prefill(self, upto=None) -> int:
+        """Consume every sequence's stream up to length ``upto`` in chunk steps: an int, [B] ints, or
+        {request prefix: [B] ints}; default on a generating plan ``prompt_len[b] - 1`` (the last
+        prompt token is the first token step's). Raises ``ValueError`` before anything is launched if
+        a target is below the sequence's present length or above C. Runs
+        ``ceil(max_b(upto_b - length_b) / Tc)`` chunk steps and returns that count; each sequence
+        ends exactly at its target. Call it on every rank alike."""
+        self._chunk_need()
+        C, Tc = self.kv_capacity, self._pp.Tc
+        targets = {}
+        for pre, st in self._kv.items():
+            if upto is None:
+                if not self._generates or max(st["plen"]) < 1:
+                    raise ValueError("prefill: give the target lengths (upto), or set_prompts on a generating plan")
+                want = [n - 1 for n in st["plen"]]
+            elif isinstance(upto, dict):
+                if pre not in upto:
+                    raise ValueError(f"prefill: no target for request {pre!r} (requests {sorted(self._kv)})")
+                want = upto[pre]
+            else:
+                want = upto
+            want = [int(want)] * st["B"] if isinstance(want, int) else [int(x) for x in want]
+            if len(want) != st["B"]:
+                raise ValueError(f"prefill: {st['B']} target lengths wanted for request {pre or '0'!r}, got {want}")
+            for b, (w, n) in enumerate(zip(want, st["len"])):
+                if w < n or w > C:
+                    raise ValueError(f"prefill: target {w} of sequence {b} of request {pre or '0'!r} is "
+                                     + (f"below its present length {n}" if w < n else f"above the capacity {C}"))
+            targets[pre] = want
+        steps = 0
+        for pre, st in self._kv.items():
+            st["limit_h"] = targets[pre]
+            steps = max(steps, max(-(-(w - n) // Tc) for w, n in zip(targets[pre], st["len"])))
+            if st["limit"] is None:
+                continue
+            if self.gpu:
+                if st["limit_ev"] is not None and not st["limit_ev"].query():
+                    st["limit_ev"].synchronize()  # the previous prefill's copy still reads the pinned buffer
+                st["limit_pin"].copy_(torch.tensor(targets[pre], dtype=torch.int32))
+                st["limit"].copy_(st["limit_pin"], non_blocking=True)
+                st["limit_ev"] = torch.cuda.Event()
+                st["limit_ev"].record()
+            else:
+                st["limit"].copy_(torch.tensor(targets[pre], dtype=torch.int32))
+        for _ in range(steps):
+            self.step_chunk()
+        return steps
+
+    def _capture_chunk(self) -> None:
+        """The chunk step as a second hipGraph, captured as the token step is (_capture)."""
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            self._chunk_body(StepStats())
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self._sync()
+        g = lifetime.keep(self, torch.cuda.CUDAGraph(keep_graph=True))
+        cur = torch.cuda.current_stream(self.device)
+        self._cap_stream.wait_stream(cur)
+        with torch.cuda.stream(self._cap_stream):
+            g.capture_begin(capture_error_mode="thread_local")
+            try:
+                self._chunk_body(StepStats())
+            finally:
+                g.capture_end()
+        cur.wait_stream(self._cap_stream)
+        self.chunk_launches = ops.ext().graph_kernel_nodes(g.raw_cuda_graph())
+        g.instantiate()
+        self._sync()
+        self._chunk_graph = g
+        self._chunk_exec = g.raw_cuda_graph_exec()
 
     def _sample(self, st: dict, logits: torch.Tensor) -> None:
         """The launch after a marked LM head: the next token of every sequence into the stream."""
@@ -3041,7 +3302,9 @@ class DAGExecutor:
 
     def generate(self, max_new_tokens: int):
         """Run ``max(prompt_len) - 1 + max_new_tokens`` steps from the present lengths (after
-        ``set_prompts``: zero) and synchronise once at the end. Returns every sequence's first
+        ``set_prompts``: zero) — on a plan with ``prefill_chunk``: ``prefill()`` (its chunk-step count
+        is kept in ``prefill_steps``) and then exactly ``max_new_tokens`` token steps — and
+        synchronise once at the end. Returns every sequence's first
         ``max_new_tokens`` generated ids, [B] lists (or {request prefix: [B] lists} with several
         requests) on the rank that holds the stream, None elsewhere. Raises before the first step
         if the prompts and the new tokens do not fit the capacity C."""
@@ -3050,13 +3313,22 @@ class DAGExecutor:
         longest = max(max(st["plen"]) for st in self._kv.values())
         if n_new < 1 or longest < 1:
             raise ValueError("generate: set_prompts first, and ask for at least one new token")
-        steps = longest - 1 + n_new
         C = self.kv_capacity
-        for st in self._kv.values():
-            if max(st["len"]) + steps * st["T"] > C or max(st["plen"]) + n_new > C:
-                raise RuntimeError(f"generate: prompts of up to {longest} tokens (lengths now {st['len']}) and "
-                                   f"{n_new} new tokens need {steps} steps and do not fit the KV cache "
-                                   f"capacity {C}")
+        if self._pp is not None:
+            # chunked prefill: every prompt but its last token in chunk steps, then exactly n_new
+            # token steps at ragged positions (each sequence samples from its own prompt's end on)
+            if longest + n_new > C:
+                raise RuntimeError(f"generate: prompts of up to {longest} tokens and {n_new} new tokens do not fit "
+                                   f"the KV cache capacity {C}")
+            self.prefill_steps = self.prefill()
+            steps = n_new
+        else:
+            steps = longest - 1 + n_new
+            for st in self._kv.values():
+                if max(st["len"]) + steps * st["T"] > C or max(st["plen"]) + n_new > C:
+                    raise RuntimeError(f"generate: prompts of up to {longest} tokens (lengths now {st['len']}) and "
+                                       f"{n_new} new tokens need {steps} steps and do not fit the KV cache "
+                                       f"capacity {C}")
         for _ in range(steps):
             self.step()
         if self.gpu:

@@ -1060,3 +1060,116 @@ def _plan_psend_waits(pr: Program, param_bytes: Dict[str, int]) -> None:
             if hit:
                 ins.wait_sends = tuple(ins.wait_sends) + tuple(x[0] for x in hit)
                 inflight = [x for x in inflight if x not in hit]
+
+
+# ------------------------------------------------------------------------------ prompt chunks
+def group_workspace_bytes(tmap: Dict[str, Task], ins: Instr, rows_mult: int = 1) -> int:
+    """Bytes of intra-group temporaries a run needs (attention qkv / o, SwiGLU gate_up, gathered
+    K/V of sequence chunks) with ``rows_mult`` times the rows of its output shape."""
+    grp = [tmap[x] for x in ins.group]
+    t = grp[1] if len(grp) > 1 and grp[0].op is not None and grp[0].op.kind in ("layernorm", "rmsnorm") else grp[0]
+    if t.op is None:
+        return 0
+    k = t.op.kind
+    M = (math.prod(t.op.out_shape[:-1]) if t.op.out_shape else 0) * rows_mult
+    a = t.op.attrs
+    if k == "attention":
+        D = a["head_dim"]
+        return 2 * (M * (a["n_head"] + 2 * a["n_kv_head"]) * D + M * a["n_head"] * D) + 512
+    if k == "swiglu_mlp":
+        return 2 * (M * 2 * a["ffn"] + M * a["ffn"]) + 512
+    if k == "attn_sp":
+        D = a["head_dim"]
+        return 2 * (M * len(t.op.inputs) * 2 * a["n_kv_head"] * D + M * a["n_head"] * D) + 1024
+    return 0
+
+
+@dataclass
+class PrefillPlan:
+    """What a chunk step of ``Tc`` tokens per sequence (runtime.plan prefill_chunk) adds to one rank:
+    the kernel groups it runs, its activation arena, and the layout of the slab that holds the
+    arena and every other buffer of the chunk shape. ``total`` is the same on every backend."""
+    Tc: int
+    runs: List[int] = field(default_factory=list)             # indices in prog.instrs of the groups a chunk step runs
+    act_offset: Dict[str, int] = field(default_factory=dict)  # output task -> byte offset in the chunk arena
+    arena_bytes: int = 0
+    ws_token: int = 0   # the token step's workspace slab
+    ws_extra: int = 0   # what the chunk step needs beyond it
+    # (key, field, shape, dtype name, bytes) in slab order; key: "@arena", "@stats", "@f8", or a request prefix
+    fields: List[Tuple[str, str, tuple, str, int]] = field(default_factory=list)
+    total: int = 0      # slab bytes (256-byte aligned fields) + ws_extra
+
+
+def _request_prefix(tid: str) -> str:
+    return tid.rsplit("/", 1)[0] + "/" if "/" in tid else ""
+
+
+def plan_prefill(tmap: Dict[str, Task], prog: Program, Tc: int) -> PrefillPlan:
+    """The chunk step of one rank. It runs only the kernel groups that contain an attention task
+    with a KV cache or an ancestor of one (the last layer's MLP, the final norm, the LM head and the
+    sampler are skipped: a chunk step produces no logits), with ``Tc`` times the rows. Its arena is
+    planned by the activation planner over those groups."""
+    pp = PrefillPlan(Tc=int(Tc))
+    keep = set()
+    stack = [t.id for t in tmap.values() if t.op is not None and t.op.kind == "attention" and "kv_cache" in t.op.attrs]
+    while stack:
+        tid = stack.pop()
+        if tid in keep or tid not in tmap:
+            continue
+        keep.add(tid)
+        stack.extend(tmap[tid].dependencies)
+    pp.runs = [i for i, ins in enumerate(prog.instrs) if ins.op == "run" and any(t in keep for t in ins.group)]
+    al = lambda n: (n + 255) // 256 * 256  # noqa: E731
+    ws_all = [group_workspace_bytes(tmap, ins) for ins in prog.instrs if ins.op == "run"]
+    pp.ws_token = max(ws_all + [256])
+    ws_chunk = max([group_workspace_bytes(tmap, prog.instrs[i], Tc) for i in pp.runs] + [0])
+    pp.ws_extra = max(0, ws_chunk - pp.ws_token)
+    if not pp.runs:
+        pp.total = pp.ws_extra
+        return pp
+    # the activation planner over the chunk groups alone, every output Tc times its bytes
+    sub = Program(rank=prog.rank, instrs=[prog.instrs[i] for i in pp.runs])
+    wide = {}
+    for ins in sub.instrs:
+        for tid in set(ins.group) | {d for t in ins.group for d in tmap[t].dependencies}:
+            if tid in tmap and tid not in wide:
+                w = tmap[tid].clone()
+                w.out_bytes = int(tmap[tid].out_bytes) * pp.Tc
+                wide[tid] = w
+    _plan_activations(_native.load(), sub, wide)
+    pp.act_offset, pp.arena_bytes = dict(sub.act_offset), int(sub.act_arena_bytes)
+    need = pp.fields
+    need.append(("@arena", "arena", (max(pp.arena_bytes, 256),), "uint8", max(pp.arena_bytes, 256)))
+    # row statistics handed from a producer GEMM to a folded norm: (sum, sum of squares) fp32 per row
+    rows = sum(math.prod(tmap[prog.instrs[i].task].op.out_shape[:-1]) * pp.Tc for i in pp.runs)
+    need.append(("@stats", "stats", (2 * rows,), "float32", 8 * rows))
+    seen, f8 = set(), 0
+    for i in pp.runs:
+        for tid in prog.instrs[i].group:
+            t = tmap[tid]
+            if t.op.kind not in ("embedding", "attention"):
+                continue
+            pre = _request_prefix(tid)
+            B = t.op.out_shape[0]
+            if pre not in seen:
+                seen.add(pre)
+                need.append((pre, "limit", (B,), "int32", 4 * B))
+            a = t.op.attrs
+            if t.op.kind == "embedding":
+                need.append((pre, "tok_g", (B * pp.Tc,), "int32", 4 * B * pp.Tc))
+                if "wpe" in t.op.weights:
+                    H = t.op.out_shape[-1]
+                    need.append((pre, "wpe_g", (B * pp.Tc, H), "bfloat16", 2 * B * pp.Tc * H))
+            else:
+                if a.get("rope") and (pre, "cos_g") not in seen:
+                    seen.add((pre, "cos_g"))
+                    D = a["head_dim"]
+                    need.append((pre, "cos_g", (B * pp.Tc, D // 2), "float32", 4 * B * pp.Tc * (D // 2)))
+                    need.append((pre, "sin_g", (B * pp.Tc, D // 2), "float32", 4 * B * pp.Tc * (D // 2)))
+                if a.get("kv_dtype", "bf16") == "fp8":
+                    f8 = max(f8, B * a["kv_cache"] * a["n_kv_head"] * a["head_dim"])
+    if f8:  # one layer's bf16 K and V cache, shared by every layer of the rank
+        need.append(("@f8", "k", (f8,), "bfloat16", 2 * f8))
+        need.append(("@f8", "v", (f8,), "bfloat16", 2 * f8))
+    pp.total = sum(al(n[4]) for n in need) + pp.ws_extra
+    return pp

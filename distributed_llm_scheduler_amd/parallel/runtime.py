@@ -17,7 +17,8 @@ from ..core import Node, get_scheduler
 from ..core.task import Task
 from ..models import registry
 from ..models.params import ParamStore, group_layout
-from .program import Program, build_programs, build_steady_programs, plan_peer_fills, steady_fill_bytes
+from .program import (Program, build_programs, build_steady_programs, plan_peer_fills, plan_prefill,
+                      steady_fill_bytes)
 
 
 @dataclass
@@ -47,6 +48,9 @@ class Plan:
     kv_cache_bytes: List[int] = field(default_factory=list)
     # plan(generate=True): bytes of the sampler's state per rank; [] without it
     sampler_bytes: List[int] = field(default_factory=list)
+    # plan(prefill_chunk=Tc): bytes the chunk step adds per rank (its activation arena, workspace
+    # beyond the token step's, gathered rows, row statistics, the fp8 dequantisation workspace)
+    prefill_bytes: List[int] = field(default_factory=list)
 
     def owner(self, tid: str) -> Optional[int]:
         """Rank holding task ``tid``'s output (a merged request resolves to its group)."""
@@ -73,7 +77,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
-         generate: bool = False) -> Plan:
+         generate: bool = False, prefill_chunk: Optional[int] = None) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -161,6 +165,16 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     (``registry.sampler_state_bytes``, ``Plan.sampler_bytes``) counts towards the cap check next to
     the caches. The key enters ``Plan.args`` only when set.
 
+    ``prefill_chunk=Tc`` (with ``kv_cache`` and ``seq == 1``, an int in 2 .. min(C, 1024); with or
+    without ``generate``, either ``kv_dtype``): the plan's executor also runs its program as a CHUNK
+    step in which every sequence consumes up to Tc tokens of its stream (``DAGExecutor.prefill`` /
+    ``step_chunk``; ``generate`` then prefills each prompt in chunk steps). The DAG, the placement,
+    the programs, the costs and the token step are those of the plan without the option. A chunk
+    step runs the kernel groups up to the last attention only; what it adds to a GPU is
+    ``Plan.prefill_bytes`` (``prefill_gb_per_rank``), counted against the cap next to the caches.
+    Refused with ``ValueError``: a plan in which a rank's program sends or receives, and one whose
+    programs re-fill parameters in the steady state. The key enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -195,6 +209,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_generate(generate, seq, kv_cache)
     if generate:  # (only when set: plans saved without it still resume, and stay as they were)
         args["generate"] = True
+    registry.check_prefill_chunk(prefill_chunk, seq, kv_cache)
+    if prefill_chunk is not None:  # (only when set, as generate)
+        args["prefill_chunk"] = prefill_chunk
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -275,7 +292,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
 
     p = place_under(caps_gb)
     if kv_cache is not None:
-        over = _kv_over_cap(p, caps_gb)
+        over = _kv_over_cap(p, caps_gb, prefill_chunk)
         if over and resume is None:
             # A policy budgets parameters against the whole cap and sees a cache only while its
             # attention task runs, but the caches persist: place once more with what this placement
@@ -283,16 +300,33 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
             reserve = [(kv + pr.act_arena_bytes) / 1e9 for kv, pr in zip(p.kv_cache_bytes, p.programs)]
             if all(caps_gb[r] > reserve[r] for r in range(world)):
                 p = place_under([caps_gb[r] - reserve[r] for r in range(world)])
-                over = _kv_over_cap(p, caps_gb)
+                over = _kv_over_cap(p, caps_gb, prefill_chunk)
         if over:
             raise ValueError(over)
     if generate:
         _check_feedback_placement(p)
+    if prefill_chunk is not None:
+        _check_chunk_programs(p)
     p.stats = plan_stats(p)
     return p
 
 
-def _kv_over_cap(p: Plan, caps_gb: Sequence[float]) -> Optional[str]:
+def _check_chunk_programs(p: Plan) -> None:
+    """plan(prefill_chunk=Tc): a chunk step runs on one GPU from resident weights."""
+    for r, pr in enumerate(p.programs):
+        n = sum(1 for i in pr.instrs if i.op in ("send", "recv"))
+        if n:
+            raise ValueError(f"prefill_chunk: the program of GPU {r} has {n} sends / receives; chunk steps across "
+                             f"ranks are not supported (world=1, or placement='replica')")
+        fill = steady_fill_bytes(pr, p.param_bytes)
+        peer = sum(1 for i in pr.instrs if i.op in ("psend",) or (i.op == "load" and i.peer >= 0))
+        if fill > 0 or peer:
+            raise ValueError(f"prefill_chunk: the program of GPU {r} re-fills parameters in the steady state "
+                             f"({fill / 1e9:.6f} GB per step, {peer} peer transfers); chunk steps need resident "
+                             f"weights (a larger cap_gb)")
+
+
+def _kv_over_cap(p: Plan, caps_gb: Sequence[float], prefill_chunk: Optional[int] = None) -> Optional[str]:
     """Sets ``p.kv_cache_bytes`` (per rank: the caches of the attention tasks placed there) and
     says which GPU, if any, cannot hold its parameter arena, activation arena and caches together:
     caches persist across tasks, unlike activations."""
@@ -304,12 +338,18 @@ def _kv_over_cap(p: Plan, caps_gb: Sequence[float]) -> Optional[str]:
             sampler[p.placement[t.id]] += registry.sampler_state_bytes(t.op)
     p.kv_cache_bytes = per_rank
     p.sampler_bytes = sampler if any(sampler) else []
+    prefill = [0] * p.world
+    if prefill_chunk is not None:
+        tmap = {t.id: t for t in p.tasks}
+        prefill = [plan_prefill(tmap, pr, prefill_chunk).total for pr in p.programs]
+        p.prefill_bytes = prefill
     for r, pr in enumerate(p.programs):
         cap = int(caps_gb[r] * 1e9)
-        if pr.param_arena_bytes + pr.act_arena_bytes + per_rank[r] + sampler[r] > cap:
+        if pr.param_arena_bytes + pr.act_arena_bytes + per_rank[r] + sampler[r] + prefill[r] > cap:
             return (f"GPU {r}: parameter arena {pr.param_arena_bytes / 1e9:.6f} GB + activation arena "
                     f"{pr.act_arena_bytes / 1e9:.6f} GB + KV caches {per_rank[r] / 1e9:.6f} GB"
                     + (f" + sampler state {sampler[r] / 1e9:.6f} GB" if sampler[r] else "")
+                    + (f" + chunk-step buffers {prefill[r] / 1e9:.6f} GB" if prefill[r] else "")
                     + f" exceed its cap of {cap / 1e9:.6f} GB")
     return None
 
@@ -389,6 +429,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["kv_dtype"] = (saved.get("kv_dtype", "bf16"), args.get("kv_dtype", "bf16"))
     if saved.get("generate", False) != args.get("generate", False):
         mismatch["generate"] = (saved.get("generate", False), args.get("generate", False))
+    if saved.get("prefill_chunk") != args.get("prefill_chunk"):
+        mismatch["prefill_chunk"] = (saved.get("prefill_chunk"), args.get("prefill_chunk"))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -583,6 +625,7 @@ def plan_stats(p: Plan) -> Dict:
         "act_arena_gb_per_rank": [pr.act_arena_bytes / 1e9 for pr in p.programs],
         **({"kv_cache_gb_per_rank": [b / 1e9 for b in p.kv_cache_bytes]} if p.kv_cache_bytes else {}),
         **({"sampler_gb_per_rank": [b / 1e9 for b in p.sampler_bytes]} if p.sampler_bytes else {}),
+        **({"prefill_gb_per_rank": [b / 1e9 for b in p.prefill_bytes]} if p.prefill_bytes else {}),
         # parameter bytes re-filled per steady-state step (evict/reload traffic of the plan)
         "refill_gb_per_step_per_rank": [steady_fill_bytes(pr, p.param_bytes) / 1e9 for pr in p.programs],
         # of which received from a peer GPU's arena over xGMI (RCCL p2p) instead of the host
@@ -725,4 +768,5 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
     # per-model GEMM choices by the canonical preset name (aliases such as "mixtral" resolve to it)
     return DAGExecutor(p.tasks, p.programs[rank], store or make_store(p), device, model_cfg=p.cfg,
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
-                       input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"))
+                       input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"),
+                       prefill_chunk=p.args.get("prefill_chunk"))

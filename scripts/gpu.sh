@@ -16,6 +16,8 @@
 #                         of the original table against the refined one
 #   stamps                in-kernel phase stamps of the GPT-2 GEMM shapes (gpubin/gemm_stamps,
 #                         built from benchmarks/gemm_stamps.hip)
+#   prefill [ARGS]        chunked prefill: time to the first token with chunk steps against token steps only,
+#                         and the chunk attention table (benchmarks/bench_prefill.py ARGS)
 # Output lands in gpurun_out/${TAG:-job}/.
 set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
@@ -136,6 +138,15 @@ case "$job" in
       done
     done
     cat $O/stamps.txt
+    ;;
+  prefill)
+    # the first-token table and the chunk attention table, each a run of its own
+    timeout -k 10 ${LIMIT:-500} python benchmarks/bench_prefill.py --skip-attention --out $O "$@" > $O/first_token.log 2>&1 \
+      || { tail -20 $O/first_token.log; exit 3; }
+    cat $O/first_token.txt
+    timeout -k 10 ${LIMIT:-500} python benchmarks/bench_prefill.py --skip-ttft --out $O "$@" > $O/attn_chunk.log 2>&1 \
+      || { tail -20 $O/attn_chunk.log; exit 4; }
+    cat $O/attn_chunk_table.txt
     ;;
   *)
     echo "unknown job $job"; exit 2
