@@ -27,6 +27,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_llm_scheduler_amd.models import registry  # noqa: E402
 from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
 
 CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, past)
@@ -34,7 +35,8 @@ CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, p
 
 def one(model, C, B, T, past, steps=10, rounds=5, kv_dtype="bf16"):
     dev = torch.device("cuda:0")
-    p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype)
+    moe = bool(registry.get_config(model).n_experts)  # an MoE model's decode steps are the plan option moe_decode
+    p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype, moe_decode=moe)
     ex = runtime.make_executor(p, 0, dev, runtime.make_store(p, device_init=runtime.device_init_ok(p, 0)))
     ex.kv_randomize(past)
     ex.step()
@@ -82,7 +84,8 @@ def generate_delta(model, C, B, past, kv_dtype="bf16", steps=10, rounds=5):
     dev = torch.device("cuda:0")
     exs = {}
     for what, gen in (("plain", False), ("generate", True)):
-        p = runtime.plan(model, world=1, seq=1, batch=B, kv_cache=C, kv_dtype=kv_dtype, generate=gen)
+        p = runtime.plan(model, world=1, seq=1, batch=B, kv_cache=C, kv_dtype=kv_dtype, generate=gen,
+                         moe_decode=bool(registry.get_config(model).n_experts))
         ex = runtime.make_executor(p, 0, dev, runtime.make_store(p, device_init=runtime.device_init_ok(p, 0)))
         ex.kv_randomize(past)
         ex.step()

@@ -120,6 +120,30 @@ void launch_gemm_glds_grouped(const GemmArgs& a, int cfg, int n_groups, const in
                               const unsigned long long* w_ptrs, const unsigned long long* c_ptrs, hipStream_t s,
                               const int* a_rows = nullptr);
 
+// Grouped skinny GEMM (gemm_grouped_skinny.hip): the contract of launch_gemm_glds_grouped for
+// bf16 without bias or residual and act in {ACT_NONE, ACT_SWIGLU}, for the <= 16 rows per group
+// of a decode step: weights streamed straight to VGPRs, a workgroup per (group, 16-column strip),
+// its waves split K and sum in a fixed order. Any counts (zero: no weight byte is requested;
+// more than 16: further passes over the same weights). K % 32 == 0, N % 16 == 0 (SwiGLU:
+// N % 32 == 0, N/2 outputs). The grid depends on (n_groups, N) only. No atomics, no host sync.
+struct GemmGroupedSkinnyArgs {
+  const void* A;  // bf16 [a_total][lda], lda % 8 == 0, 16-byte aligned
+  int lda;
+  int a_total;         // rows of A (a_rows values are clamped into it)
+  const int* a_rows;   // device int32 [R] or nullptr
+  const int* offsets;  // device int32 [n_groups + 1]
+  const unsigned long long* w_ptrs;  // device [n_groups]: bf16 [N][K], 16-byte aligned
+  const unsigned long long* c_ptrs;  // device [n_groups] or nullptr
+  void* C;                           // bf16 [R][ldc] when c_ptrs == nullptr
+  int ldc;
+  int compact_rows;
+  int R, N, K;  // R: rows all groups cover together (offsets are clamped to it)
+  int act;
+  int n_groups;
+};
+bool gemm_grouped_skinny_takes(int N, int K, int act);
+void launch_gemm_grouped_skinny(const GemmGroupedSkinnyArgs& a, hipStream_t s);
+
 // W8A16 GEMM (gemm_w8.hip): C = act(alpha * scale[n] * sum_k A[m][k] * Wq[n][k] + bias[n]) + R
 // with Wq stored as OCP e4m3 bytes ([N][ldw], K contiguous) and one fp32 scale per output
 // channel. The fp8 bytes go through LDS, are converted to bf16 in registers (exact) and run on

@@ -1288,6 +1288,74 @@ void gemm_grouped(const at::Tensor& x, const std::vector<at::Tensor>& weights, c
                            arp);
 }
 
+// gemm_grouped on the skinny kernel (gemm_grouped_skinny.hip): the same tensors and checks; what
+// the kernel does not take (bias-free bf16, act none / SwiGLU, K % 32 == 0, N % 16 == 0 — SwiGLU
+// N % 32 == 0 —, 16-byte aligned rows) is refused here.
+void gemm_grouped_skinny(const at::Tensor& x, const std::vector<at::Tensor>& weights, const at::Tensor& w_ptrs,
+                         const at::Tensor& offsets, int64_t act, const c10::optional<at::Tensor>& out,
+                         const std::vector<at::Tensor>& outs, const c10::optional<at::Tensor>& out_ptrs,
+                         const c10::optional<at::Tensor>& a_rows) {
+  const int64_t E = (int64_t)weights.size();
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  TORCH_CHECK(E > 0, "at least one expert");
+  const int* arp = nullptr;
+  if (a_rows.has_value()) {
+    TORCH_CHECK(a_rows->is_cuda() && a_rows->scalar_type() == at::kInt && a_rows->is_contiguous(),
+                "a_rows: contiguous int32 on the GPU");
+    arp = a_rows->data_ptr<int32_t>();
+  }
+  const int64_t R = a_rows.has_value() ? a_rows->numel() : x.size(0), K = x.size(1), N = weights[0].size(0);
+  const bool sw = act == kActSwiglu;
+  const int64_t NO = sw ? N / 2 : N;
+  TORCH_CHECK(gemm_grouped_skinny_takes((int)N, (int)K, (int)act),
+              "skinny grouped GEMM: act none or SwiGLU, K % 32 == 0, N % 16 == 0 (SwiGLU: N % 32 == 0)");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "skinny grouped GEMM: rows of x must be 16-byte aligned");
+  for (const auto& w : weights) {
+    check_bf16(w, "expert weight");
+    TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == N && w.size(1) == K, "expert weights [N][K]");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0, "expert weights must be 16-byte aligned");
+  }
+  TORCH_CHECK(w_ptrs.is_cuda() && w_ptrs.scalar_type() == at::kLong && w_ptrs.numel() == E, "w_ptrs int64 [E]");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kInt && offsets.numel() == E + 1,
+              "offsets int32 [E+1]");
+  GemmGroupedSkinnyArgs g{};
+  g.A = x.data_ptr();
+  g.lda = (int)x.stride(0);
+  g.a_total = (int)x.size(0);
+  g.a_rows = arp;
+  g.offsets = offsets.data_ptr<int32_t>();
+  g.w_ptrs = reinterpret_cast<const unsigned long long*>(w_ptrs.data_ptr<int64_t>());
+  g.R = (int)R;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.act = (int)act;
+  g.n_groups = (int)E;
+  if (out_ptrs.has_value()) {
+    TORCH_CHECK((int64_t)outs.size() == E && out_ptrs->is_cuda() && out_ptrs->scalar_type() == at::kLong &&
+                    out_ptrs->numel() == E,
+                "compact outputs: E tensors + int64 [E] addresses");
+    const int64_t cap = outs[0].size(0);
+    for (const auto& o : outs) {
+      check_bf16(o, "expert output");
+      TORCH_CHECK(o.dim() == 2 && o.is_contiguous() && o.size(1) == NO && o.size(0) == cap,
+                  "expert outputs: E contiguous [cap][N'] tensors");
+    }
+    g.ldc = (int)NO;
+    g.compact_rows = (int)cap;
+    g.c_ptrs = reinterpret_cast<const unsigned long long*>(out_ptrs->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(out.has_value(), "grouped GEMM needs `out` or compact outputs");
+    check_bf16(*out, "out");
+    check_rows(*out, "out");
+    TORCH_CHECK(out->size(0) == R && out->size(1) == NO, "out must be [R][N'] (N' = N/2 with SwiGLU)");
+    g.C = out->data_ptr();
+    g.ldc = (int)out->stride(0);
+  }
+  launch_gemm_grouped_skinny(g, cur_stream());
+}
+
 // gemm_grouped with fp8 expert weights (gemm_w8_grouped.hip): weights E x e4m3 [N][K], scales
 // E x fp32 [N]; w_ptrs / s_ptrs / out_ptrs: int64 [E] device tensors of their addresses (cached
 // by the caller: hipGraph-safe). config < 0: picked by (rows_hint, N, K).
@@ -1767,4 +1835,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act") = 0, py::arg("out") = py::none(), py::arg("outs") = std::vector<at::Tensor>{},
         py::arg("out_ptrs") = py::none(), py::arg("config") = -1, py::arg("a_rows") = py::none(),
         py::arg("shared_weights") = false);
+  m.def("gemm_grouped_skinny", &gemm_grouped_skinny, py::arg("x"), py::arg("weights"), py::arg("w_ptrs"),
+        py::arg("offsets"), py::arg("act") = 0, py::arg("out") = py::none(),
+        py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(), py::arg("a_rows") = py::none());
 }

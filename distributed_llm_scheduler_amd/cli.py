@@ -31,7 +31,9 @@ mxfp4-experts = MXFP4 for the expert weights of an MoE model only, needs --act-d
 --act-dtype {bf16,fp8} (fp8, with --weight-dtype fp8, mxfp4 or mxfp4-experts: GEMM inputs quantised per row,
 multiplied on the block-scaled MFMA against the fp8 or fp4 weight), --kv-cache C (decode steps: --seq is
 the number of new tokens per step and every attention node keeps a KV cache of C positions),
---kv-dtype {bf16,fp8} (with --kv-cache: fp8 = e4m3 cache bytes + one fp32 scale per position and KV head) and, for
+--kv-dtype {bf16,fp8} (with --kv-cache: fp8 = e4m3 cache bytes + one fp32 scale per position and KV head),
+--moe-decode (with --kv-cache and an MoE model: decode steps of a Mixtral plan, the expert GEMMs of a step of a
+few token rows on the skinny grouped kernel) and, for
 ``run``, --past P (the caches are filled with random rows to length P before the timed steps).
 """
 from __future__ import annotations
@@ -78,7 +80,11 @@ def _common(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--kv-cache", type=int, default=None, metavar="C",
                     help="decode steps: --seq becomes the number of new tokens per step (1 .. 16) and every attention "
                          "node keeps K/V caches of C positions per sequence on its GPU; the caches count against "
-                         "--hbm-cap-gb (dense gpt2 / llama models; no --tp / --sp)")
+                         "--hbm-cap-gb (dense gpt2 / llama models, MoE models with --moe-decode; no --tp / --sp)")
+    ap.add_argument("--moe-decode", action="store_true",
+                    help="with --kv-cache and an MoE model (bf16 weights): decode steps of the MoE DAG; a step of at "
+                         "most ops.MOE_SKINNY_MAX_ROWS token rows (1: one sequence, one token) runs both grouped expert "
+                         "launches of every MoE layer on the weight-streaming skinny kernel")
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="with --kv-cache: how the caches are stored: bf16, or fp8 (OCP e4m3 + one fp32 power-of-two "
                          "scale per position and KV head: (head_dim + 4) / (2 head_dim) of the bf16 bytes)")
@@ -95,7 +101,7 @@ def _plan(a, world: int, resume: Optional[str] = None):
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
                         placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
                         act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None),
-                        kv_dtype=getattr(a, "kv_dtype", "bf16"))
+                        kv_dtype=getattr(a, "kv_dtype", "bf16"), moe_decode=getattr(a, "moe_decode", False))
 
 
 def _has_kv(p) -> bool:
@@ -382,7 +388,8 @@ def cmd_generate(a) -> int:
     if a.prompt_len < 1 or a.new < 1 or a.prompt_len + a.new > a.kv_cache:
         raise SystemExit(f"--prompt-len {a.prompt_len} + --new {a.new} must be positive and fit --kv-cache {a.kv_cache}")
     p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
-                     kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk)
+                     kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk,
+                     moe_decode=a.moe_decode)
     store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
     prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
@@ -489,6 +496,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--no-graph", action="store_true")
     g.add_argument("--prefill-chunk", type=int, default=None, metavar="Tc",
                    help="consume the prompts in chunk steps of Tc tokens per sequence (2 .. min(C, 1024))")
+    g.add_argument("--moe-decode", action="store_true", help="an MoE model's decode steps (see run --moe-decode)")
     g.set_defaults(fn=cmd_generate)
     a = ap.parse_args(argv)
     return a.fn(a)

@@ -97,12 +97,14 @@ KV_MAX_STEP = 16  # new tokens per step the decode attention kernel takes
 KV_MAX_COLS = 64  # (n_head / n_kv_head) * new tokens: its query columns per KV head
 
 
-def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: int = 1) -> None:
-    """What a KV cache of ``kv_cache`` positions with ``seq`` new tokens per step does not combine with."""
+def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: int = 1, moe_decode: bool = False) -> None:
+    """What a KV cache of ``kv_cache`` positions with ``seq`` new tokens per step does not combine
+    with. An MoE model takes decode steps only with ``moe_decode=True`` (see :func:`check_moe_decode`)."""
     if not isinstance(kv_cache, int) or isinstance(kv_cache, bool) or kv_cache < 1:
         raise ValueError(f"kv_cache must be a positive number of positions, got {kv_cache!r}")
-    if cfg.n_experts:
-        raise ValueError(f"kv_cache: MoE models ({cfg.name}) have no decode step yet (dense gpt2 / llama models only)")
+    if cfg.n_experts and not moe_decode:
+        raise ValueError(f"kv_cache: MoE models ({cfg.name}) take decode steps only with moe_decode=True "
+                         "(--moe-decode); without it the cache covers dense gpt2 / llama models only")
     if tp > 1 or sp > 1:
         raise ValueError("kv_cache does not combine with tensor or sequence parallelism (tp, sp > 1): a cache "
                          "belongs to one attention node on one GPU")
@@ -116,6 +118,25 @@ def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: i
     if rep * seq > KV_MAX_COLS:
         raise ValueError(f"kv_cache: (n_head / n_kv_head) * seq = {rep} * {seq} exceeds the decode attention "
                          f"kernel's {KV_MAX_COLS} query rows per KV head")
+
+
+def check_moe_decode(moe_decode: bool, cfg: ModelConfig, kv_cache: "int | None", weight_dtype: str = "bf16",
+                     prefill_chunk=None) -> None:
+    """What ``moe_decode=True`` (decode steps of an MoE model over the KV cache, the expert GEMMs
+    of a step of a few token rows on the skinny grouped kernel: ops.MOE_SKINNY_MAX_ROWS) needs of a plan."""
+    if not moe_decode:
+        return
+    if kv_cache is None:
+        raise ValueError("moe_decode=True needs a KV cache (kv_cache=C): it is the decode step of an MoE model")
+    if not cfg.n_experts:
+        raise ValueError(f"moe_decode=True needs an MoE model; {cfg.name} has no experts (its decode steps need "
+                         "no option)")
+    if weight_dtype != "bf16":
+        raise ValueError(f"moe_decode=True takes weight_dtype='bf16' only, got {weight_dtype!r}: quantised experts "
+                         "keep their own grouped kernels, which have no skinny form yet")
+    if prefill_chunk is not None:
+        raise ValueError("moe_decode=True does not combine with prefill_chunk: a chunk step's bit-identical repeat "
+                         "has not been shown for the routing and combine launches of an MoE layer")
 
 
 KV_DTYPES = ("bf16", "fp8")
@@ -219,7 +240,8 @@ def add_kv_cache(tasks: List[Task], batch: int, seq: int, kv_cache: int, cost_mo
 def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_model: str = "bytes",
           tp: int = 1, sp: int = 1, weight_dtype: str = "bf16", act_dtype: str = "bf16",
           kv_cache: "int | None" = None,
-          kv_dtype: str = "bf16", generate: bool = False) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          kv_dtype: str = "bf16", generate: bool = False,
+          moe_decode: bool = False) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
@@ -239,7 +261,9 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     ``kv_dtype="fp8"`` (needs ``kv_cache``; independent of ``weight_dtype`` / ``act_dtype``): the
     caches hold e4m3 bytes and one fp32 scale per (position, KV head) (:func:`kv_cache_bytes`).
     ``generate=True`` (needs ``kv_cache`` and ``seq == 1``): every request's ``lm_head`` op carries
-    ``attrs["sample"]``, the request's ordinal, and the executor samples the next token after it."""
+    ``attrs["sample"]``, the request's ordinal, and the executor samples the next token after it.
+    ``moe_decode=True`` (needs ``kv_cache``, an MoE model and ``weight_dtype="bf16"``): lifts the
+    cache's refusal of MoE models (:func:`check_moe_decode`); the DAG is the model's own."""
     check_kv_dtype(kv_dtype, kv_cache)
     check_generate(generate, seq, kv_cache)
     known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
@@ -272,8 +296,9 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         if tp > 1 or sp > 1:
             raise ValueError(f"weight_dtype={weight_dtype!r} does not combine with tensor or sequence parallelism "
                              "(tp, sp > 1)")
+    check_moe_decode(moe_decode, cfg, kv_cache, weight_dtype)
     if kv_cache is not None:
-        check_kv_cache(cfg, seq, kv_cache, tp, sp)
+        check_kv_cache(cfg, seq, kv_cache, tp, sp, moe_decode)
     tasks: List[Task] = []
     for r in range(replicas):
         tasks.extend(build_dag(cfg, batch, seq, cost_model, prefix=f"r{r}/" if replicas > 1 else ""))

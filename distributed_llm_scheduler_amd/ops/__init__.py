@@ -1363,6 +1363,76 @@ def gemm_grouped(x, weights, offsets, act=None, out=None, outs=None, w_ptrs=None
     return out if outs is None else outs
 
 
+# Token rows of a decode step up to which the executor sends the two grouped expert launches of
+# an MoE layer to the skinny kernel. The kernel takes any count and a pass of it covers 16 rows, but
+# the bound is what was measured at Mixtral's shapes (benchmarks/bench_moe_decode.py,
+# profiles/moe_decode/): the largest M up to which the skinny kernel is the faster in every
+# alternating pair against gemm_grouped for BOTH launches (gate/up ties above M = 1: both kernels
+# stream the routed weights at 5.7 TB/s) and the captured decode step with it is the faster in
+# every alternating round (at 2, 8 and 16 rows the step with a skinny down launch alone was slower).
+MOE_SKINNY_MAX_ROWS = 1
+
+
+def grouped_skinny_ok(N: int, K: int, act=None) -> bool:
+    """Does the skinny grouped kernel take an [N][K] expert weight with this activation?"""
+    a = ACT[act] if not isinstance(act, int) else act
+    if a not in (0, SWIGLU) or N <= 0 or K <= 0 or K % 32:
+        return False
+    return N % 32 == 0 if a == SWIGLU else N % 16 == 0
+
+
+def gemm_grouped_skinny(x, weights, offsets, act=None, out=None, outs=None, w_ptrs=None, out_ptrs=None, a_rows=None):
+    """``gemm_grouped`` for the at most 16 rows per expert of a decode step (GPU: the
+    weight-streaming kernel of gemm_grouped_skinny.hip, grid = experts x 16-column strips, fixed
+    by (E, N) alone). Same arguments and results as ``gemm_grouped``: expert e multiplies the
+    sorted rows [offsets[e], offsets[e+1]) of ``x`` (token rows ``a_rows[r]`` when given) by
+    ``weights[e]`` and writes them at the same rows of ``out`` or compactly into ``outs[e]``.
+    bf16, ``act`` None or "swiglu", K % 32 == 0, N % 16 == 0 (SwiGLU: N % 32 == 0); any other
+    shape raises ``ValueError``. Any row counts are legal: an expert without rows reads no weight
+    byte, one with more than 16 takes further passes over its weight."""
+    a = ACT[act] if not isinstance(act, int) else act
+    E = len(weights)
+    if E == 0:
+        raise ValueError("gemm_grouped_skinny: at least one expert")
+    if weights[0].dim() != 2 or x.dim() != 2:
+        raise ValueError("gemm_grouped_skinny: x [rows][K] and expert weights [N][K]")
+    N, K = weights[0].shape
+    if a not in (0, SWIGLU):
+        raise ValueError(f"gemm_grouped_skinny: act must be None or 'swiglu', not {act!r}")
+    if not grouped_skinny_ok(N, K, a):
+        raise ValueError(f"gemm_grouped_skinny: N = {N}, K = {K} not taken: K % 32 == 0 and N % 16 == 0 "
+                         "(SwiGLU: N % 32 == 0)")
+    if x.shape[1] != K or any(tuple(w.shape) != (N, K) for w in weights):
+        raise ValueError("gemm_grouped_skinny: every expert weight must be [N][K] with K = x.shape[1]")
+    if x.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in weights):
+        raise ValueError("gemm_grouped_skinny: bf16 only")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise ValueError("gemm_grouped_skinny: rows of x must be contiguous and 16-byte aligned (row stride % 8 == 0)")
+    if any(not w.is_contiguous() or w.data_ptr() % 16 for w in weights):
+        raise ValueError("gemm_grouped_skinny: expert weights must be contiguous and 16-byte aligned")
+    if offsets.numel() != E + 1 or offsets.dtype != torch.int32:
+        raise ValueError("gemm_grouped_skinny: offsets int32 [E+1]")
+    if a_rows is not None and a_rows.dtype != torch.int32:
+        raise ValueError("gemm_grouped_skinny: a_rows int32")
+    if (out is None) == (outs is None):
+        raise ValueError("gemm_grouped_skinny: exactly one of `out` and `outs`")
+    NO = N // 2 if a == SWIGLU else N
+    R = x.shape[0] if a_rows is None else a_rows.numel()
+    if out is not None and tuple(out.shape) != (R, NO):
+        raise ValueError(f"gemm_grouped_skinny: out must be [{R}][{NO}]")
+    if outs is not None and (len(outs) != E or any(o.dim() != 2 or o.shape[1] != NO for o in outs)):
+        raise ValueError(f"gemm_grouped_skinny: outs must be E tensors [cap][{NO}]")
+    if _gpu(x):
+        if w_ptrs is None:
+            w_ptrs = torch.tensor([w.data_ptr() for w in weights], dtype=torch.int64, device=x.device)
+        if outs is not None and out_ptrs is None:
+            out_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=x.device)
+        ext().gemm_grouped_skinny(x, list(weights), w_ptrs, offsets, a, out, list(outs) if outs is not None else [],
+                                  out_ptrs, a_rows)
+        return out if outs is None else outs
+    return gemm_grouped(x, weights, offsets, act=a, out=out, outs=outs, a_rows=a_rows)
+
+
 def w8_grouped_configs() -> int:
     """Number of tile configurations of the grouped fp8-weight GEMM (``gemm_grouped_w8(config=...)``)."""
     return int(ext().gemm_w8_grouped_num_configs())

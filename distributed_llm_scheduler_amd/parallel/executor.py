@@ -149,6 +149,10 @@ MOE_XBATCH = os.environ.get("DLS_MOE_XBATCH", "1") != "0"
 # MoE routing in one launch (router + align, ops.moe_route) and the grouped gate/up GEMM
 # gathering its token rows itself (no permute kernel); 0 restores the separate launches
 MOE_FUSED_ROUTE = os.environ.get("DLS_MOE_FUSED_ROUTE", "1") != "0"
+# decode steps of an MoE plan (runtime.plan moe_decode=True) with at most ops.MOE_SKINNY_MAX_ROWS
+# token rows: a layer's two grouped expert launches on the weight-streaming skinny kernel
+# (ops.gemm_grouped_skinny); 0 keeps the grouped kernels of full steps
+MOE_SKINNY = os.environ.get("DLS_MOE_SKINNY", "1") != "0"
 # an unfolded norm (K > FOLD_MAX_K) computed by the block that produces its input: the split-K
 # reduce of the residual GEMM (or the MoE combine) owns whole rows and writes norm(row) too
 POST_NORM = os.environ.get("DLS_POST_NORM", "1")  # "0" off, "1" every producer, "gemm" residual GEMMs only
@@ -465,6 +469,8 @@ class DAGExecutor:
         self._moe_skip: set = set()
         self._moe_batched_ids: set = set()
         self._moe_bufs: Dict[int, tuple] = {}
+        # batch (its first instruction) -> which of its launches took the skinny kernel: ("gate_up", "down")
+        self._moe_skinny: Dict[int, Tuple[str, ...]] = {}
         self._gate_route: Dict[str, Tuple[int, int]] = {}  # router task -> (E, top-k): GEMM + routing fused
         ins = self.prog.instrs
         if not self.gpu or not MOE_BATCH or any(i.op == "evict" or (i.op == "load" and i.peer >= 0) for i in ins):
@@ -710,6 +716,14 @@ class DAGExecutor:
             cached = (ptrs, mk(w13), mk(w2), mk(outs))
             self._moe_bufs[i] = cached
         hbuf = self._scratch("moe_h", (R, F))
+        if (MOE_SKINNY and self.kv_capacity is not None and R // K <= ops.MOE_SKINNY_MAX_ROWS
+                and ops.grouped_skinny_ok(2 * F, x.shape[1], "swiglu") and ops.grouped_skinny_ok(w2[0].shape[0], F)):
+            # a decode step of one token row (ops.MOE_SKINNY_MAX_ROWS): top_k experts have a row, the
+            # others none — both launches stream the routed experts' weights only (gemm_grouped_skinny.hip)
+            self._moe_skinny[i] = ("gate_up", "down")
+            ops.gemm_grouped_skinny(x, w13, off, act="swiglu", out=hbuf, w_ptrs=cached[1], a_rows=rows)
+            ops.gemm_grouped_skinny(hbuf, w2, off, outs=outs, w_ptrs=cached[2], out_ptrs=cached[3])
+            return
         ops.gemm_grouped(x, w13, off, act="swiglu", out=hbuf, w_ptrs=cached[1], rows_hint=max(1, R // E), a_rows=rows)
         ops.gemm_grouped(hbuf, w2, off, outs=outs, w_ptrs=cached[2], out_ptrs=cached[3], rows_hint=max(1, R // E))
 

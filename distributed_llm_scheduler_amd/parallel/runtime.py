@@ -77,7 +77,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
-         generate: bool = False, prefill_chunk: Optional[int] = None) -> Plan:
+         generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -175,6 +175,19 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     Refused with ``ValueError``: a plan in which a rank's program sends or receives, and one whose
     programs re-fill parameters in the steady state. The key enters ``Plan.args`` only when set.
 
+    ``moe_decode=True`` (with ``kv_cache``, an MoE model and ``weight_dtype="bf16"``; with or
+    without ``generate``, either ``kv_dtype``): decode steps of an MoE model. Without the option an
+    MoE model with ``kv_cache`` is refused as before. The step is the model's own DAG over
+    ``batch * seq`` token rows — router, fused routing, grouped expert GEMMs, combine — around the
+    cached attention; with at most ``ops.MOE_SKINNY_MAX_ROWS`` token rows (1: measured, see its
+    comment) the executor issues both grouped expert launches of every layer through
+    ``ops.gemm_grouped_skinny`` (``DLS_MOE_SKINNY=0``, and any larger step: the grouped kernels of
+    full steps).
+    Every other cache restriction holds. Refused with ``ValueError``: no ``kv_cache``, a model
+    without experts, a ``weight_dtype`` other than ``"bf16"``, and ``prefill_chunk``. A capped plan (its programs evict and
+    re-fill parameters), a plan with ``DLS_MOE_BATCH=0`` and a step of more than 16 token rows run
+    the expert kernels of full steps. The key enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -212,6 +225,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_prefill_chunk(prefill_chunk, seq, kv_cache)
     if prefill_chunk is not None:  # (only when set, as generate)
         args["prefill_chunk"] = prefill_chunk
+    registry.check_moe_decode(moe_decode, registry.get_config(model), kv_cache, weight_dtype, prefill_chunk)
+    if moe_decode:  # (only when set, as generate)
+        args["moe_decode"] = True
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -227,7 +243,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
                                         sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache,
-                                        kv_dtype=kv_dtype, generate=generate)
+                                        kv_dtype=kv_dtype, generate=generate, moe_decode=moe_decode)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
 
     def place_under(caps_now: Sequence[float]) -> Plan:
@@ -431,6 +447,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["generate"] = (saved.get("generate", False), args.get("generate", False))
     if saved.get("prefill_chunk") != args.get("prefill_chunk"):
         mismatch["prefill_chunk"] = (saved.get("prefill_chunk"), args.get("prefill_chunk"))
+    if saved.get("moe_decode", False) != args.get("moe_decode", False):
+        mismatch["moe_decode"] = (saved.get("moe_decode", False), args.get("moe_decode", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}

@@ -18,6 +18,9 @@
 #                         built from benchmarks/gemm_stamps.hip)
 #   prefill [ARGS]        chunked prefill: time to the first token with chunk steps against token steps only,
 #                         and the chunk attention table (benchmarks/bench_prefill.py ARGS)
+#   moe-decode [ARGS]     the skinny grouped expert GEMM against ops.gemm_grouped at Mixtral's shapes, and the
+#                         mixtral-8x7b-1l decode step with the skinny launches off and on
+#                         (benchmarks/bench_moe_decode.py ARGS)
 # Output lands in gpurun_out/${TAG:-job}/.
 set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
@@ -147,6 +150,15 @@ case "$job" in
     timeout -k 10 ${LIMIT:-500} python benchmarks/bench_prefill.py --skip-ttft --out $O "$@" > $O/attn_chunk.log 2>&1 \
       || { tail -20 $O/attn_chunk.log; exit 4; }
     cat $O/attn_chunk_table.txt
+    ;;
+  moe-decode)
+    # the kernel table and the step A/B, each a run of its own
+    timeout -k 10 ${LIMIT:-500} python benchmarks/bench_moe_decode.py --out $O "$@" > $O/kernels.log 2>&1 \
+      || { tail -20 $O/kernels.log; exit 3; }
+    cat $O/kernels.txt
+    timeout -k 10 ${LIMIT:-500} python benchmarks/bench_moe_decode.py --skip-kernels --step --out $O > $O/step.log 2>&1 \
+      || { tail -20 $O/step.log; exit 4; }
+    cat $O/step.txt
     ;;
   *)
     echo "unknown job $job"; exit 2
