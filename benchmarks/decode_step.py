@@ -8,12 +8,19 @@ microsecond of event overhead) — for T new tokens per step from a context of P
 share of the step is the baseline a GEMV path would be measured against.
 
     python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--kv-dtype fp8] [--only B,T,past]
-                                     [--out FILE] [--generate]
+                                     [--out FILE] [--generate] [--skinny-gemm [--max-rows N]]
 
 --kv-dtype fp8: the caches hold e4m3 bytes and per-(position, KV head) scales (runtime.plan kv_dtype).
 --generate: instead of the breakdown, the T = 1 cases with and without on-device sampling
 (runtime.plan generate=True; temperature 0.8, top_k 50, top_p 0.9, and greedy) in one session, the
 captured steps alternating, and the difference.
+
+--skinny-gemm: instead of the breakdown, every case as one captured graph of the plan with
+skinny_gemm=True and one of the plan without it, in one process: five alternating rounds of ten
+steps, the medians, the ratio and in how many rounds the step with the option was the faster. The
+default cases are then SKINNY_CASES (llama3-8b-1l) or GPT2_SKINNY_CASES (--model gpt2). --max-rows N
+sets ops.SKINNY_MAX_ROWS for the run (a bound search; the default measures what the executor does),
+--lm-head 0/1 ops.SKINNY_LMHEAD.
 
 Needs a GPU.
 """
@@ -31,6 +38,8 @@ from distributed_llm_scheduler_amd.models import registry  # noqa: E402
 from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
 
 CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, past)
+SKINNY_CASES = [(1, 1, 512), (1, 1, 8000), (2, 1, 8000), (4, 1, 8000), (8, 1, 8000), (16, 1, 8000), (1, 16, 8000)]
+GPT2_SKINNY_CASES = [(1, 1, 512), (8, 1, 1000)]
 
 
 def one(model, C, B, T, past, steps=10, rounds=5, kv_dtype="bf16"):
@@ -123,6 +132,57 @@ def generate_delta(model, C, B, past, kv_dtype="bf16", steps=10, rounds=5):
     return [line]
 
 
+def skinny_delta(model, C, B, T, past, kv_dtype="bf16", steps=10, rounds=5):
+    """us per captured step of the plan without and with skinny_gemm=True, the two graphs alternating."""
+    from distributed_llm_scheduler_amd import ops
+
+    dev = torch.device("cuda:0")
+    moe = bool(registry.get_config(model).n_experts)
+    exs, store = {}, None
+    for what, flag in (("tiles", False), ("skinny", True)):
+        p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype, moe_decode=moe,
+                         **(dict(skinny_gemm=True) if flag else {}))
+        store = store or runtime.make_store(p, device_init=runtime.device_init_ok(p, 0))
+        ex = runtime.make_executor(p, 0, dev, store)
+        ex.kv_randomize(past)
+        ex.step()
+        ex.kv_reset(past)
+        if not ex.capture():
+            raise RuntimeError("the decode step was not captured")
+        exs[what] = ex
+    assert past + steps * T <= C
+    ran = sorted(w for (_, w), v in exs["skinny"]._skinny.items() if v == "skinny")
+    fell = sorted({v for v in exs["skinny"]._skinny.values() if v != "skinny"})
+
+    def timed(ex):
+        ex.kv_reset(past)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            ex.step()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / steps * 1e3
+
+    t = {"tiles": [], "skinny": []}
+    for _ in range(rounds):
+        for what in ("tiles", "skinny"):
+            t[what].append(timed(exs[what]))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    wins = sum(a < b for a, b in zip(t["skinny"], t["tiles"]))
+    line = (f"{model}  B {B}  T {T}  past {past}  cache {C} ({kv_dtype}): {med['tiles']:.1f} us per step on the tiles "
+            f"({exs['tiles'].launches} launches; min {min(t['tiles']):.1f}, max {max(t['tiles']):.1f}), "
+            f"{med['skinny']:.1f} us with skinny_gemm ({exs['skinny'].launches} launches; min {min(t['skinny']):.1f}, "
+            f"max {max(t['skinny']):.1f}): {med['tiles'] / med['skinny']:.3f}x, faster in {wins} of {rounds} rounds; "
+            f"{len(ran)} GEMMs skinny (stream={exs['skinny']._skinny_stream}), fallbacks: {fell or 'none'}; "
+            f"SKINNY_MAX_ROWS {ops.SKINNY_MAX_ROWS}, SKINNY_LMHEAD {ops.SKINNY_LMHEAD}; medians of {rounds} alternating "
+            f"rounds of {steps} steps")
+    del exs, store
+    torch.cuda.empty_cache()
+    return [line]
+
+
 def step_breakdown(model="llama3-8b-1l", C=8192, kv_dtype="bf16", cases=CASES):
     out = []
     for B, T, past in cases:
@@ -139,11 +199,29 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--generate", action="store_true",
                     help="the T = 1 cases with and without on-device sampling, alternating, and the difference")
+    ap.add_argument("--skinny-gemm", action="store_true",
+                    help="every case with and without the plan option skinny_gemm, the captured steps alternating")
+    ap.add_argument("--max-rows", type=int, default=None, help="with --skinny-gemm: ops.SKINNY_MAX_ROWS for this run")
+    ap.add_argument("--lm-head", type=int, default=None, help="with --skinny-gemm: ops.SKINNY_LMHEAD for this run (0 / 1)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("decode_step.py needs a GPU")
     cases = [tuple(int(x) for x in a.only.split(","))] if a.only else CASES
-    if a.generate:
+    if a.skinny_gemm:
+        from distributed_llm_scheduler_amd import ops
+
+        if a.max_rows is not None:
+            ops.SKINNY_MAX_ROWS = a.max_rows  # (read by the executor at every launch)
+        if a.lm_head is not None:
+            ops.SKINNY_LMHEAD = bool(a.lm_head)
+        if not a.only:
+            cases = GPT2_SKINNY_CASES if a.model.startswith("gpt2") else SKINNY_CASES
+        lines = []
+        for B, T, past in cases:
+            lines += skinny_delta(a.model, min(a.kv_cache, registry.get_config(a.model).n_positions), B, T, past,
+                                  a.kv_dtype)
+            print(lines[-1], flush=True)
+    elif a.generate:
         lines = []
         for B, T, past in cases:
             if T == 1:

@@ -144,6 +144,40 @@ struct GemmGroupedSkinnyArgs {
 bool gemm_grouped_skinny_takes(int N, int K, int act);
 void launch_gemm_grouped_skinny(const GemmGroupedSkinnyArgs& a, hipStream_t s);
 
+// Dense skinny GEMM (gemm_skinny.hip): C = epi(alpha * A W^T) for the 1 <= M <= 16 rows of a decode
+// step, bf16, weights streamed straight to VGPRs: a workgroup per 16-column strip of the output
+// (SwiGLU: per 16-gate + 16-up block pair), its `waves` waves split K and sum in a fixed order. No
+// atomics, no split-K across workgroups, no workspace. Any N (SwiGLU: N % 32 == 0), K % 32 == 0,
+// lda % 8 == 0, ldw % 8 == 0, A and W 16-byte aligned. With ln_mode 1 (LayerNorm) / 2 (RMSNorm) A
+// holds the raw rows, W / bias / ln_colsum the derived operands of a folded norm, and the kernel
+// takes the row statistics itself. Row ranges, compact outputs, stats_out, ext_stats and
+// post-norms are not part of the contract.
+constexpr int kSkinnyMaxRows = 16;
+struct GemmSkinnyArgs {
+  const void* A;  // bf16 [M][lda]
+  int lda;
+  const void* W;  // bf16 [N][ldw]
+  int ldw;
+  void* C;  // bf16 [M][ldc] (SwiGLU: N/2 columns)
+  int ldc;
+  const void* bias;  // bf16 [N] or nullptr
+  const void* R;     // bf16 [M][ldr] or nullptr
+  int ldr;
+  int M, N, K;
+  int act;  // DlsAct
+  float alpha;
+  RopeArgs rope{};
+  const float* ln_colsum = nullptr;  // fp32 [N]
+  int ln_mode = 0;
+  float ln_eps = 1e-5f;
+  int stream = 0;  // weight loads: 1 streaming (nt), 0 default cache policy
+  int waves = 0;   // 4, 8, 16; 0: gemm_skinny_waves
+};
+// false with *why (optional) naming the rule a launch breaks
+bool gemm_skinny_takes(const GemmSkinnyArgs& a, const char** why = nullptr);
+int gemm_skinny_waves(int N, int K, int act);  // waves per workgroup the launcher picks: 4, 8 or 16
+bool launch_gemm_skinny(const GemmSkinnyArgs& a, hipStream_t s);  // false: nothing launched
+
 // W8A16 GEMM (gemm_w8.hip): C = act(alpha * scale[n] * sum_k A[m][k] * Wq[n][k] + bias[n]) + R
 // with Wq stored as OCP e4m3 bytes ([N][ldw], K contiguous) and one fp32 scale per output
 // channel. The fp8 bytes go through LDS, are converted to bf16 in registers (exact) and run on

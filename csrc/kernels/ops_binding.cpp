@@ -1356,6 +1356,103 @@ void gemm_grouped_skinny(const at::Tensor& x, const std::vector<at::Tensor>& wei
   launch_gemm_grouped_skinny(g, cur_stream());
 }
 
+// Dense skinny GEMM (gemm_skinny.hip) for the M <= 16 rows of a decode step. The rule a shape breaks
+// as text ("" when the kernel takes it): ops.skinny_ok / ops.linear_skinny turn it into a ValueError.
+GemmSkinnyArgs skinny_shape(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t act, int64_t rope_S,
+                            int64_t rope_D, int64_t rope_cols, int64_t ln_mode, int64_t waves) {
+  GemmSkinnyArgs g{};
+  g.lda = (int)lda;
+  g.ldw = (int)ldw;
+  g.M = (int)std::min<int64_t>(M, 1 << 30);
+  g.N = (int)std::min<int64_t>(N, 1 << 30);
+  g.K = (int)std::min<int64_t>(K, 1 << 30);
+  g.ldc = g.ldr = g.N;
+  g.act = (int)act;
+  g.rope = RopeArgs{nullptr, nullptr, (int)rope_S, (int)rope_D, (int)rope_cols};
+  g.ln_mode = (int)ln_mode;
+  static const float dummy = 0.f;
+  g.ln_colsum = ln_mode != 0 ? &dummy : nullptr;
+  g.waves = (int)waves;
+  return g;
+}
+std::string gemm_skinny_refusal(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t act, int64_t rope_S,
+                                int64_t rope_D, int64_t rope_cols, int64_t ln_mode, int64_t waves) {
+  const char* why = nullptr;
+  gemm_skinny_takes(skinny_shape(M, N, K, lda, ldw, act, rope_S, rope_D, rope_cols, ln_mode, waves), &why);
+  return why ? why : "";
+}
+int64_t gemm_skinny_waves_py(int64_t N, int64_t K, int64_t act) { return gemm_skinny_waves((int)N, (int)K, (int)act); }
+
+at::Tensor gemm_skinny(const at::Tensor& a_in, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
+                       const c10::optional<at::Tensor>& residual, int64_t act, double alpha,
+                       const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& ln_colsum,
+                       int64_t ln_mode, double ln_eps, const c10::optional<at::Tensor>& rope_cos,
+                       const c10::optional<at::Tensor>& rope_sin, int64_t rope_S, int64_t rope_D, int64_t rope_cols,
+                       bool stream, int64_t waves) {
+  check_bf16(a_in, "A");
+  check_bf16(w, "W");
+  at::Tensor a = as2d(a_in);
+  check_rows(a, "A");
+  check_rows(w, "W");
+  const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K && w.device() == a.device(), "W must be [N][K] with K = ", K, " on A's device");
+  GemmSkinnyArgs g = skinny_shape(M, N, K, a.stride(0), w.stride(0), act, rope_S, rope_D, rope_cols, ln_mode, waves);
+  const char* why = nullptr;
+  TORCH_CHECK(gemm_skinny_takes(g, &why), "skinny GEMM: ", why ? why : "");
+  const int64_t NO = act == kActSwiglu ? N / 2 : N;
+  at::Tensor c;
+  if (out.has_value()) {
+    c = as2d(*out);
+    check_bf16(c, "out");
+    TORCH_CHECK(c.size(0) == M && c.size(1) == NO && c.stride(1) == 1 && c.device() == a.device(),
+                "out must be [M][N_out]");
+  } else {
+    c = at::empty({M, NO}, a.options());
+  }
+  g.A = a.data_ptr();
+  g.W = w.data_ptr();
+  g.C = c.data_ptr();
+  g.ldc = (int)c.stride(0);
+  g.bias = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == a.device(), "bias must be contiguous [N]");
+    g.bias = bias->data_ptr();
+  }
+  g.R = nullptr;
+  g.ldr = 0;
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1 && r.device() == a.device(),
+                "residual must be [M][N_out]");
+    g.R = r.data_ptr();
+    g.ldr = (int)r.stride(0);
+  }
+  g.alpha = (float)alpha;
+  g.ln_eps = (float)ln_eps;
+  g.ln_colsum = nullptr;
+  if (ln_mode != 0) {
+    TORCH_CHECK(ln_colsum.has_value() && ln_colsum->is_cuda() && ln_colsum->scalar_type() == at::kFloat &&
+                    ln_colsum->is_contiguous() && ln_colsum->numel() == N && ln_colsum->device() == a.device(),
+                "folded norm needs fp32 ln_colsum [N]");
+    g.ln_colsum = ln_colsum->data_ptr<float>();
+  }
+  if (rope_cols > 0) {
+    TORCH_CHECK(rope_cos.has_value() && rope_sin.has_value() && rope_cos->scalar_type() == at::kFloat &&
+                    rope_sin->scalar_type() == at::kFloat && rope_cos->is_contiguous() && rope_sin->is_contiguous() &&
+                    rope_cos->is_cuda() && rope_sin->is_cuda() &&
+                    rope_cos->numel() >= rope_S * rope_D / 2 && rope_sin->numel() >= rope_S * rope_D / 2,
+                "RoPE epilogue: cos/sin fp32 [S][D/2]");
+    g.rope.cos = rope_cos->data_ptr<float>();
+    g.rope.sin = rope_sin->data_ptr<float>();
+  }
+  g.stream = stream ? 1 : 0;
+  TORCH_CHECK(gemm_skinny_takes(g, &why), "skinny GEMM: ", why ? why : "");
+  TORCH_CHECK(launch_gemm_skinny(g, cur_stream()), "skinny GEMM refused the launch");
+  return c;
+}
+
 // gemm_grouped with fp8 expert weights (gemm_w8_grouped.hip): weights E x e4m3 [N][K], scales
 // E x fp32 [N]; w_ptrs / s_ptrs / out_ptrs: int64 [E] device tensors of their addresses (cached
 // by the caller: hipGraph-safe). config < 0: picked by (rows_hint, N, K).
@@ -1838,4 +1935,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_grouped_skinny", &gemm_grouped_skinny, py::arg("x"), py::arg("weights"), py::arg("w_ptrs"),
         py::arg("offsets"), py::arg("act") = 0, py::arg("out") = py::none(),
         py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(), py::arg("a_rows") = py::none());
+  m.def("gemm_skinny", &gemm_skinny, py::arg("a"), py::arg("w"), py::arg("bias") = py::none(),
+        py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0, py::arg("out") = py::none(),
+        py::arg("ln_colsum") = py::none(), py::arg("ln_mode") = 0, py::arg("ln_eps") = 1e-5,
+        py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_S") = 1,
+        py::arg("rope_D") = 4, py::arg("rope_cols") = 0, py::arg("stream") = false, py::arg("waves") = 0);
+  m.def("gemm_skinny_refusal", &gemm_skinny_refusal, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
+        py::arg("ldw"), py::arg("act") = 0, py::arg("rope_S") = 1, py::arg("rope_D") = 4, py::arg("rope_cols") = 0,
+        py::arg("ln_mode") = 0, py::arg("waves") = 0);
+  m.def("gemm_skinny_waves", &gemm_skinny_waves_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
 }

@@ -33,7 +33,8 @@ multiplied on the block-scaled MFMA against the fp8 or fp4 weight), --kv-cache C
 the number of new tokens per step and every attention node keeps a KV cache of C positions),
 --kv-dtype {bf16,fp8} (with --kv-cache: fp8 = e4m3 cache bytes + one fp32 scale per position and KV head),
 --moe-decode (with --kv-cache and an MoE model: decode steps of a Mixtral plan, the expert GEMMs of a step of a
-few token rows on the skinny grouped kernel) and, for
+few token rows on the skinny grouped kernel), --skinny-gemm (with --kv-cache and bf16 weights: the dense GEMMs of
+a step of a few token rows on the weight-streaming skinny kernel) and, for
 ``run``, --past P (the caches are filled with random rows to length P before the timed steps).
 """
 from __future__ import annotations
@@ -85,6 +86,10 @@ def _common(ap: argparse.ArgumentParser) -> None:
                     help="with --kv-cache and an MoE model (bf16 weights): decode steps of the MoE DAG; a step of at "
                          "most ops.MOE_SKINNY_MAX_ROWS token rows (1: one sequence, one token) runs both grouped expert "
                          "launches of every MoE layer on the weight-streaming skinny kernel")
+    ap.add_argument("--skinny-gemm", action="store_true",
+                    help="with --kv-cache (bf16 weights): the dense GEMMs of a step of at most ops.SKINNY_MAX_ROWS "
+                         "token rows run on the weight-streaming skinny kernel (ops.linear_skinny) instead of the "
+                         "prefill tiles")
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="with --kv-cache: how the caches are stored: bf16, or fp8 (OCP e4m3 + one fp32 power-of-two "
                          "scale per position and KV head: (head_dim + 4) / (2 head_dim) of the bf16 bytes)")
@@ -101,7 +106,8 @@ def _plan(a, world: int, resume: Optional[str] = None):
                         batch=a.batch, seq=a.seq, cost_model=a.cost_model, fuse=not a.no_fuse,
                         placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
                         act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None),
-                        kv_dtype=getattr(a, "kv_dtype", "bf16"), moe_decode=getattr(a, "moe_decode", False))
+                        kv_dtype=getattr(a, "kv_dtype", "bf16"), moe_decode=getattr(a, "moe_decode", False),
+                        skinny_gemm=getattr(a, "skinny_gemm", False))
 
 
 def _has_kv(p) -> bool:
@@ -389,7 +395,7 @@ def cmd_generate(a) -> int:
         raise SystemExit(f"--prompt-len {a.prompt_len} + --new {a.new} must be positive and fit --kv-cache {a.kv_cache}")
     p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
                      kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk,
-                     moe_decode=a.moe_decode)
+                     moe_decode=a.moe_decode, skinny_gemm=a.skinny_gemm)
     store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
     prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
@@ -497,6 +503,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--prefill-chunk", type=int, default=None, metavar="Tc",
                    help="consume the prompts in chunk steps of Tc tokens per sequence (2 .. min(C, 1024))")
     g.add_argument("--moe-decode", action="store_true", help="an MoE model's decode steps (see run --moe-decode)")
+    g.add_argument("--skinny-gemm", action="store_true",
+                   help="the dense GEMMs of the token step on the skinny kernel (see run --skinny-gemm)")
     g.set_defaults(fn=cmd_generate)
     a = ap.parse_args(argv)
     return a.fn(a)

@@ -139,6 +139,22 @@ def check_moe_decode(moe_decode: bool, cfg: ModelConfig, kv_cache: "int | None",
                          "has not been shown for the routing and combine launches of an MoE layer")
 
 
+def check_skinny_gemm(skinny_gemm: bool, kv_cache: "int | None", weight_dtype: str = "bf16") -> None:
+    """What ``skinny_gemm=True`` (the dense GEMMs of a decode step of at most ops.SKINNY_MAX_ROWS
+    token rows on the weight-streaming skinny kernel, ops.linear_skinny) needs of a plan. Every
+    model family, both ``kv_dtype``s, ``generate``, ``prefill_chunk`` (the token step takes the
+    kernel, the chunk step keeps the tiles), MoE models with ``moe_decode`` (their dense GEMMs)
+    and capped plans are accepted."""
+    if not skinny_gemm:
+        return
+    if kv_cache is None:
+        raise ValueError("skinny_gemm=True needs a KV cache (kv_cache=C): the skinny kernel is for the at most 16 "
+                         "token rows of a decode step")
+    if weight_dtype != "bf16":
+        raise ValueError(f"skinny_gemm=True takes weight_dtype='bf16' only, got {weight_dtype!r}: the quantised GEMMs "
+                         "have no skinny form yet")
+
+
 KV_DTYPES = ("bf16", "fp8")
 
 

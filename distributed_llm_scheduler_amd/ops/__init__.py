@@ -599,6 +599,148 @@ def linear_norm(x, w_derived, colsum, bias_derived, mode, eps=1e-5, act=None, re
     return y.view(shp) if out is None else out
 
 
+# ------------------------------------------------------------- dense skinny GEMM (M <= 16)
+
+SKINNY_ROWS_LIMIT = 16  # rows the kernel of gemm_skinny.hip takes (one token fragment per wave)
+SKINNY_WAVES = (4, 8, 16)  # its instances: waves per workgroup = ways K is split inside it
+# Token rows of a decode step up to which the executor sends dense GEMMs to the skinny kernel, and
+# whether vocabulary-sized projections (N >= LMHEAD_MIN_N) go there too: set by the measurements of
+# profiles/skinny_gemm/ (README, "Dense skinny GEMM"). The captured llama3-8b-1l step with every
+# dense GEMM skinny won every alternating round at 1 and 2 rows (1.08x), 4 of 5 at 4 rows, none at
+# 8 and 16 (step_bound_search.txt): 2. The LM-head rows of the kernel table (kernels.txt) won every
+# pair at M = 1, 2 and 4 on both models (Llama's 1.05 GB head: 162 against 197 us at M = 1), and the
+# step without the skinny LM head is a tie with the tiles (step_lmhead_off.txt): True.
+SKINNY_MAX_ROWS = 2
+SKINNY_LMHEAD = True
+_NORM_MODE = {"layernorm": 1, "rmsnorm": 2, 1: 1, 2: 2}
+
+
+def skinny_waves(N: int, K: int, act=None) -> int:
+    """Waves per workgroup ``linear_skinny`` launches with (the rule of gemm_skinny_waves in
+    gemm_skinny.hip, mirrored here for the CPU back end), read off the kernel table of
+    profiles/skinny_gemm/: 4 for SwiGLU, 16 for a vocabulary-sized N at K >= 2048, else 8."""
+    a = ACT[act] if not isinstance(act, int) else act
+    strips = N // 32 if a == SWIGLU else (N + 15) // 16
+    nk = (K + 63) // 64
+    if a == SWIGLU:
+        return 4
+    return 16 if strips >= 4096 and nk >= 32 else 8
+
+
+def skinny_refusal(M, N, K, act=None, rope=None, norm=None, waves=None, lda=None, ldw=None) -> Optional[str]:
+    """Why the skinny kernel does not take a launch (None: it does) — the rules of
+    gemm_skinny_takes in gemm_skinny.hip."""
+    try:
+        a = ACT[act] if not isinstance(act, int) else act
+    except KeyError:
+        return f"unknown activation {act!r}"
+    lda, ldw = (K if lda is None else lda), (K if ldw is None else ldw)
+    if not 1 <= M <= SKINNY_ROWS_LIMIT:
+        return f"M = {M}: the kernel takes 1..{SKINNY_ROWS_LIMIT} rows"
+    if N < 1 or K < 32 or K % 32:
+        return f"N = {N}, K = {K}: N >= 1 and K a positive multiple of 32"
+    if lda % 8 or ldw % 8 or lda < K or ldw < K:
+        return "row strides of x and w must be multiples of 8 elements"
+    if a not in (0, 1, 2, 3, SWIGLU):
+        return f"unknown activation {act!r}"
+    if a == SWIGLU and N % 32:
+        return f"SwiGLU needs N % 32 == 0, N = {N}"
+    if rope is not None:
+        _, _, S, D, cols = rope
+        if a != 0 or cols <= 0 or cols % 4 or cols > N or D < 4 or D % 4 or cols % D or S < 1:
+            return "RoPE needs no activation, cols % 4 == 0, whole heads (cols % D == 0) and D % 4 == 0"
+    if norm is not None and norm[1] not in _NORM_MODE:
+        return f"norm mode {norm[1]!r}: 'layernorm' or 'rmsnorm'"
+    if waves is not None and waves not in SKINNY_WAVES:
+        return f"waves = {waves}: one of {SKINNY_WAVES}"
+    return None
+
+
+def skinny_ok(M, N, K, act=None, rope=None, norm=None, waves=None, lda=None, ldw=None) -> bool:
+    """Does the dense skinny kernel take an [M][K] x [N][K]^T launch with this epilogue?"""
+    return skinny_refusal(M, N, K, act, rope, norm, waves, lda, ldw) is None
+
+
+def _ref_linear_skinny(x, w, bias, act, residual, alpha, rope, norm):
+    """fp32 reference of linear_skinny on the operands the kernel receives; a folded norm takes
+    its row statistics from x."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if norm is None:
+        return ref_linear(x, w, bias, a, residual, alpha, rope=rope)
+    colsum, mode, eps = norm
+    xf = x.float()
+    K = x.shape[-1]
+    y = alpha * (xf @ w.float().t())
+    ms = xf.pow(2).sum(-1, keepdim=True) / K
+    if _NORM_MODE[mode] == 1:
+        mu = xf.sum(-1, keepdim=True) / K
+        y = torch.rsqrt((ms - mu * mu).clamp_min(0) + eps) * (y - mu * colsum.float())
+    else:
+        y = torch.rsqrt(ms + eps) * y
+    if bias is not None:
+        y = y + bias.float()
+    if rope is not None:
+        y = _rope_ref_pairs(y.reshape(-1, y.shape[-1]), rope).reshape(y.shape)
+    y = _swiglu_interleaved(y) if a == SWIGLU else _act_ref(y, a)
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(x.dtype)
+
+
+def linear_skinny(x, w, bias=None, act=None, residual=None, alpha=1.0, out=None, rope=None, norm=None, stream=False,
+                  waves=None, **refused):
+    """``act(alpha * x @ w^T + bias) + residual`` for the 1 <= M <= 16 rows of a decode step on the
+    weight-streaming kernel of gemm_skinny.hip (GPU): a workgroup per 16-column strip, ``waves``
+    waves (4, 8, 16; None: :func:`skinny_waves`) split K inside it and sum in a fixed order — no
+    atomics, no workspace, two launches bit-identical, and a row's result does not depend on the
+    other rows of the launch. Same operands as :func:`linear`: ``act="swiglu"`` takes the gate/up
+    interleaved weight, ``rope=(cos, sin, S, D, cols)`` rotates pair-interleaved columns.
+    ``norm=(colsum, mode, eps)`` folds a LayerNorm / RMSNorm of x's rows into the launch: ``w``,
+    ``bias`` and ``colsum`` are the derived operands of :func:`derive_norm_gemm`, x holds the RAW
+    rows and the kernel takes the row statistics itself. ``stream``: weight loads with the
+    streaming (nt) cache policy — for weights that cannot stay in the Infinity Cache anyway.
+    What the kernel does not take raises ``ValueError``: M > 16, K % 32 != 0, SwiGLU with
+    N % 32 != 0, operands that are not bf16 or not 16-byte aligned rows, and the ``rows`` /
+    ``compact`` / ``stats_out`` / ``ext_stats`` / ``post_norm`` arguments of :func:`linear`."""
+    for k, v in refused.items():
+        if k not in ("rows", "rows_hint", "compact", "stats_out", "ext_stats", "post_norm"):
+            raise TypeError(f"linear_skinny() got an unexpected keyword argument {k!r}")
+        if v is not None and v is not False and k != "rows_hint":
+            raise ValueError(f"linear_skinny: `{k}` is not part of the skinny kernel's contract")
+    if x.dim() < 2 or w.dim() != 2 or w.shape[1] != x.shape[-1]:
+        raise ValueError("linear_skinny: x [..., K] and w [N][K]")
+    a = ACT.get(act, -1) if not isinstance(act, int) else act
+    K, N = x.shape[-1], w.shape[0]
+    M = x.numel() // K
+    x2 = x.reshape(M, K)
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise ValueError("linear_skinny: bf16 operands only")
+    if x2.stride(1) != 1 or w.stride(1) != 1 or x2.data_ptr() % 16 or w.data_ptr() % 16:
+        raise ValueError("linear_skinny: rows of x and w must be contiguous and 16-byte aligned")
+    why = skinny_refusal(M, N, K, a if a >= 0 else act, rope, norm, waves, x2.stride(0) if M > 1 else K, w.stride(0))
+    if why is not None:
+        raise ValueError(f"linear_skinny: {why}")
+    n_out = N // 2 if a == SWIGLU else N
+    for name, t, shp in (("bias", bias, (N,)), ("residual", residual, (M, n_out)), ("out", out, (M, n_out))):
+        if t is not None and (t.dtype != torch.bfloat16 or t.numel() != math.prod(shp)):
+            raise ValueError(f"linear_skinny: {name} must be bf16 {list(shp)}")
+    if norm is not None and (norm[0].dtype != torch.float32 or norm[0].numel() != N):
+        raise ValueError("linear_skinny: norm = (fp32 colsum [N], mode, eps)")
+    r2 = residual if residual is None or residual.dim() == 2 else residual.reshape(M, n_out)
+    o2 = out if out is None or out.dim() == 2 else out.view(M, n_out)
+    if _gpu(x):
+        rc, rs_, rS, rD, rcols = rope if rope is not None else (None, None, 1, 4, 0)
+        cs, m, eps = (norm[0], _NORM_MODE[norm[1]], float(norm[2])) if norm is not None else (None, 0, 1e-5)
+        y = ext().gemm_skinny(x2, w, bias, r2, a, float(alpha), o2, cs, m, eps, rc, rs_, int(rS), int(rD), int(rcols),
+                              bool(stream), int(waves or 0))
+        return y.view(x.shape[:-1] + (n_out,)) if out is None else out
+    y = _ref_linear_skinny(x2, w, bias, a, r2, alpha, rope, norm).reshape(x.shape[:-1] + (n_out,))
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
 def mlp_fused_ok(M, H, F, Hout) -> bool:
     """Does the one-launch MLP block (gemm_fused.hip) take this shape on this GPU?"""
     return bool(ext().mlp_fused_ok(int(M), int(H), int(F), int(Hout)))

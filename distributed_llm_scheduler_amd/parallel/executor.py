@@ -196,8 +196,22 @@ class DAGExecutor:
                  trace: bool = False, debug: bool = False, model_name: Optional[str] = None,
                  input_parts: Optional[Dict[str, List[str]]] = None,
                  requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16",
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None, skinny_gemm: bool = False):
         self.tasks = {t.id: t for t in tasks}
+        # runtime.plan skinny_gemm=True: the dense bf16 GEMMs of a step of at most ops.SKINNY_MAX_ROWS
+        # token rows go to ops.linear_skinny (_skinny_pick). DLS_SKINNY=0 turns the dispatch off (the
+        # launches of the plan without the option), DLS_SKINNY=all takes every step of up to 16 rows
+        # and the LM head whatever the two measured constants say.
+        self.skinny_gemm = bool(skinny_gemm)
+        self._skinny_mode = os.environ.get("DLS_SKINNY", "1")
+        self._skinny_on = self.skinny_gemm and torch.device(device).type == "cuda" and self._skinny_mode != "0"
+        self._skinny: Dict[Tuple[str, str], str] = {}  # (task, weight) -> "skinny" or why the tiles ran
+        # rows of the token step: above the dispatch's limit no GEMM of it runs skinny, and the step
+        # keeps the launches of the plan without the option, statistics hand-off included
+        rows = max([math.prod(t.op.out_shape[:-1]) for t in tasks
+                    if t.op is not None and t.op.kind in ("linear", "lm_head", "attention", "swiglu_mlp")] or [0])
+        self._skinny_rows = rows <= (ops.SKINNY_ROWS_LIMIT if self._skinny_mode == "all" else ops.SKINNY_MAX_ROWS)
+        self._cur_task: Optional[str] = None           # head task of the kernel group in flight
         # runtime.plan prefill_chunk=Tc: the program also runs as a chunk step of Tc tokens per sequence
         self.prefill_chunk = int(prefill_chunk) if prefill_chunk else None
         self._chunk_on = False  # a chunk step is being issued (_chunk_mode)
@@ -317,6 +331,11 @@ class DAGExecutor:
         g = GUARD_BYTES if self.debug else 0
         self._act_full = torch.empty(max(p.act_arena_bytes, 256) + g, dtype=torch.uint8, device=dev)
         self._param_full = torch.empty(max(p.param_arena_bytes, 256) + g, dtype=torch.uint8, device=dev)
+        # skinny GEMMs load their weights with the default cache policy. The rule this started from —
+        # streaming (nt) loads iff the rank's parameters exceed the 256 MB Infinity Cache and cannot
+        # stay there from step to step anyway — measured SLOWER at every Llama-3-8B shape (5-10 %:
+        # profiles/skinny_gemm/kernels.txt), so nt is only what DLS_SKINNY_STREAM=1 asks for (A/B).
+        self._skinny_stream = os.environ.get("DLS_SKINNY_STREAM", "0") == "1"
         self.act_slab = self._act_full[:self._act_full.numel() - g]
         self.param_slab = self._param_full[:self._param_full.numel() - g]
         if g:
@@ -880,7 +899,12 @@ class DAGExecutor:
                 # the consumer's weight (width > FOLD_MAX_K, i.e. DLS_HANDOFF_MAX_K raised); up to
                 # FOLD_MAX_K the norm is folded either way and the consumer GEMM accumulates the
                 # statistics in its main loop: the same launches, no unordered sum.
-                if self.prefill_chunk and width <= FOLD_MAX_K:
+                # A plan with skinny_gemm whose token step is small enough to run skinny takes no
+                # hand-off either: the skinny kernel sums x's rows itself, in a fixed order, and emits
+                # no statistics for the next GEMM. Above FOLD_MAX_K a hand-off that remains sends its
+                # two GEMMs to the tiles (_skinny_pick). (A larger token step keeps the hand-off: on
+                # the tiles its loss costs GPT-2's B 8 step 20 %, profiles/skinny_gemm/step_first_run.txt.)
+                if (self.prefill_chunk or (self._skinny_on and self._skinny_rows)) and width <= FOLD_MAX_K:
                     continue
                 if pi is not None and emits(pi) and src not in need and width <= HANDOFF_MAX_K:
                     need.append(src)
@@ -1335,6 +1359,9 @@ class DAGExecutor:
             return y
         ext = self._ext_stats.get(norm.op.inputs[0]) if norm is not None else None
         shared = self._w_users.get(w_name, 1) > 1
+        # the fold decision below is what it is without the option (a weight folded in place must be
+        # folded for every reader): the skinny kernel only replaces the launch
+        skinny = self._skinny_pick(x, w_name, act, rope, stats_out, ext)
         if norm is not None and self.gpu and (ext is not None or x.shape[-1] <= FOLD_MAX_K) \
                 and not (shared and self._refills()):
             # (a shared weight's folded copy is private: a step that re-fills its group would
@@ -1342,6 +1369,10 @@ class DAGExecutor:
             # folded norm: statistics handed over by x's producer (any K, split-K allowed), or
             # accumulated in this GEMM's main loop (K <= FOLD_MAX_K)
             W, cs, bd = self._prep(w_name, norm, b_name, interleave=sw, rope_perm=rope_perm)
+            if skinny:  # the folded operands, the row statistics taken in the kernel
+                return ops.linear_skinny(x, W, bd, act=act, residual=residual, out=out, rope=rope,
+                                         norm=(cs, norm.op.kind, norm.op.attrs.get("eps", 1e-5)),
+                                         stream=self._skinny_stream)
             return ops.linear_norm(x, W, cs, bd, norm.op.kind, norm.op.attrs.get("eps", 1e-5), act=act,
                                    residual=residual, out=out, rope=rope, ext_stats=ext)
         if norm is not None and self._pn_given == norm.id:  # x's producer wrote the normalised rows
@@ -1365,7 +1396,44 @@ class DAGExecutor:
                 # the same for every reader of a shared weight, e.g. DLS_HANDOFF_MAX_K > FOLD_MAX_K
                 # with a replica whose input came from a peer without row statistics)
                 raise RuntimeError(f"{w_name}: unfolded GEMM over a weight another reader transformed in place")
+        if skinny:
+            return ops.linear_skinny(x, W, bias, act=act, residual=residual, out=out, rope=rope,
+                                     stream=self._skinny_stream)
         return ops.linear(x, W, bias, act=act, residual=residual, out=out, rope=rope, stats_out=stats_out)
+
+    def _skinny_pick(self, x, w_name, act=None, rope=None, stats_out=None, ext=None) -> bool:
+        """Does the GEMM of the group in flight on weight ``w_name`` go to ops.linear_skinny? A plan
+        with skinny_gemm on a GPU, a token step of at most ops.SKINNY_MAX_ROWS rows (a chunk step
+        keeps the tiles), a bf16 weight, a shape the kernel takes, no row statistics handed over on
+        either side, and not a vocabulary-sized projection unless ops.SKINNY_LMHEAD. The answer or
+        the reason of the fallback is kept in ``_skinny[(task, weight)]``."""
+        if not self._skinny_on or self._chunk_on:
+            return False
+        W = self._w(w_name)
+        M, K, N = x.numel() // x.shape[-1], x.shape[-1], W.shape[0]
+        every = self._skinny_mode == "all"
+        limit = ops.SKINNY_ROWS_LIMIT if every else ops.SKINNY_MAX_ROWS
+        why = None
+        if W.dtype != torch.bfloat16:
+            why = f"{str(W.dtype).replace('torch.', '')} weight"
+        elif M > limit:
+            why = f"M = {M} rows, above {limit}"
+        elif stats_out is not None or ext is not None:
+            why = "row statistics handed over"
+        elif N >= ops.LMHEAD_MIN_N and not (every or ops.SKINNY_LMHEAD):
+            why = "vocabulary-sized projection (ops.SKINNY_LMHEAD)"
+        else:
+            why = ops.skinny_refusal(M, N, K, act, rope, lda=x.stride(0) if M > 1 else K, ldw=W.stride(0))
+        self._skinny[(self._cur_task, w_name)] = why or "skinny"
+        return why is None
+
+    def _pn_for(self, x, w_name, out2d, stats_out=None):
+        """``post_norm`` of a residual GEMM: a GEMM that runs skinny writes no post-norm and must
+        not claim the norm (_pn_done), so the consumer runs its norm launch — as it does whenever
+        the norm's weights are not resident."""
+        if self._skinny_pick(x, w_name, stats_out=stats_out):
+            return None
+        return self._post_norm_out(out2d)
 
     def _linear(self, x, w_name, b_name=None, act=None, residual=None, out=None, stats_out=None, post_norm=None,
                 interleave: bool = False, xq=None):
@@ -1377,6 +1445,8 @@ class DAGExecutor:
         bias = self._w(b_name) if b_name else None
         mx = W.dtype == torch.uint8  # the stored format decides: an mxfp4 weight's e2m1 pairs
         if W.dtype != torch.float8_e4m3fn and not mx:
+            if post_norm is None and self._skinny_pick(x, w_name, act, None, stats_out):
+                return ops.linear_skinny(x, W, bias, act=act, residual=residual, out=out, stream=self._skinny_stream)
             return ops.linear(x, W, bias, act=act, residual=residual, out=out, stats_out=stats_out,
                               post_norm=post_norm)
         if stats_out is not None or post_norm is not None:
@@ -1587,6 +1657,7 @@ class DAGExecutor:
         if len(grp) > 1 and grp[0].op.kind in ("layernorm", "rmsnorm"):
             norm, grp = grp[0], grp[1:]
         head, tail = grp[0], grp[-1]
+        self._cur_task = head.id
         out = self._views[tail.id]
         k = head.op.kind
         residual = None
@@ -1672,7 +1743,7 @@ class DAGExecutor:
                     ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o,
                                          workspace=self._kv_ws, k_scale=ks, v_scale=vs)
                 self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
-                             post_norm=self._post_norm_out(self._flat(out)))
+                             post_norm=self._pn_for(o, W["w_o"], self._flat(out), st_out))
                 return
             if self._attn_block_ok(head, norm, x, residual, out, B, S):
                 W1, cs, bd = self._prep(W["w_qkv"], norm, W.get("b_qkv"))
@@ -1693,7 +1764,7 @@ class DAGExecutor:
             ops.attention(qkv[:, :nh * D], qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], B, S, nh, nkv,
                           D, causal=a.get("causal", True), out=o)
             self._linear(o, W["w_o"], W.get("b_o"), residual=residual, out=self._flat(out), stats_out=st_out,
-                         post_norm=self._post_norm_out(self._flat(out)))
+                         post_norm=self._pn_for(o, W["w_o"], self._flat(out), st_out))
         elif k == "qkv_proj":
             # sequence chunk c's QKV rows (RoPE at its absolute positions c*Sc ..)
             x = self._flat(self._x(src))
@@ -1732,7 +1803,7 @@ class DAGExecutor:
             h = self._ws(0, (M, F))
             self._gemm(x, W["w_gate_up"], None, norm, act="swiglu", out=h)  # SwiGLU in the epilogue
             self._linear(h, W["w_down"], residual=residual, out=self._flat(out), stats_out=st_out,
-                         post_norm=self._post_norm_out(self._flat(out)))
+                         post_norm=self._pn_for(h, W["w_down"], self._flat(out), st_out))
         elif k == "moe_expert":
             self._moe_expert(head, self._flat(out))
         elif k == "moe_combine":

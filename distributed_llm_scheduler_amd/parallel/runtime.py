@@ -77,7 +77,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          placement: str = "scheduler", tp: int = 1, resume: Optional[str] = None, sp: int = 1,
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
-         generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False) -> Plan:
+         generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False,
+         skinny_gemm: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -188,6 +189,16 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     re-fill parameters), a plan with ``DLS_MOE_BATCH=0`` and a step of more than 16 token rows run
     the expert kernels of full steps. The key enters ``Plan.args`` only when set.
 
+    ``skinny_gemm=True`` (with ``kv_cache`` and ``weight_dtype="bf16"``; any model family, either
+    ``kv_dtype``, with or without ``generate``, ``prefill_chunk`` and ``moe_decode``): the executor
+    sends the dense bf16 GEMMs of a step of at most ``ops.SKINNY_MAX_ROWS`` token rows (QKV,
+    out-projection, gate/up, down, and with ``ops.SKINNY_LMHEAD`` the LM head) to the
+    weight-streaming kernel of ``ops.linear_skinny`` instead of the prefill tiles; norms folded
+    today stay folded (the kernel takes the row statistics itself), a chunk step keeps the tiles.
+    The DAG, the placement, the programs and the costs are those of the plan without the option.
+    Refused with ``ValueError``: no ``kv_cache``, a ``weight_dtype`` other than ``"bf16"``. The key
+    enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -228,6 +239,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_moe_decode(moe_decode, registry.get_config(model), kv_cache, weight_dtype, prefill_chunk)
     if moe_decode:  # (only when set, as generate)
         args["moe_decode"] = True
+    registry.check_skinny_gemm(skinny_gemm, kv_cache, weight_dtype)
+    if skinny_gemm:  # (only when set, as generate: the executor's choice of kernel, nothing the DAG sees)
+        args["skinny_gemm"] = True
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -449,6 +463,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["prefill_chunk"] = (saved.get("prefill_chunk"), args.get("prefill_chunk"))
     if saved.get("moe_decode", False) != args.get("moe_decode", False):
         mismatch["moe_decode"] = (saved.get("moe_decode", False), args.get("moe_decode", False))
+    if saved.get("skinny_gemm", False) != args.get("skinny_gemm", False):
+        mismatch["skinny_gemm"] = (saved.get("skinny_gemm", False), args.get("skinny_gemm", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -787,4 +803,4 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
     return DAGExecutor(p.tasks, p.programs[rank], store or make_store(p), device, model_cfg=p.cfg,
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
                        input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"),
-                       prefill_chunk=p.args.get("prefill_chunk"))
+                       prefill_chunk=p.args.get("prefill_chunk"), skinny_gemm=p.args.get("skinny_gemm", False))

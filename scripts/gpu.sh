@@ -21,6 +21,9 @@
 #   moe-decode [ARGS]     the skinny grouped expert GEMM against ops.gemm_grouped at Mixtral's shapes, and the
 #                         mixtral-8x7b-1l decode step with the skinny launches off and on
 #                         (benchmarks/bench_moe_decode.py ARGS)
+#   skinny [ARGS]        the dense skinny GEMM against ops.linear / ops.linear_norm at the Llama-3-8B and GPT-2
+#                         decode shapes (benchmarks/bench_skinny.py ARGS), then the llama3-8b-1l and gpt2 decode
+#                         steps with and without the plan option (benchmarks/decode_step.py --skinny-gemm)
 # Output lands in gpurun_out/${TAG:-job}/.
 set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-$(pwd)}"
@@ -159,6 +162,18 @@ case "$job" in
     timeout -k 10 ${LIMIT:-500} python benchmarks/bench_moe_decode.py --skip-kernels --step --out $O > $O/step.log 2>&1 \
       || { tail -20 $O/step.log; exit 4; }
     cat $O/step.txt
+    ;;
+  skinny)
+    # the kernel table and the two step tables, each a run of its own
+    timeout -k 10 ${LIMIT:-560} python benchmarks/bench_skinny.py --out $O "$@" > $O/kernels.log 2>&1 \
+      || { tail -20 $O/kernels.log; exit 3; }
+    cat $O/kernels.txt
+    timeout -k 10 ${LIMIT:-400} python benchmarks/decode_step.py --skinny-gemm --out $O/step_llama3-8b-1l.txt > $O/step_llama.log 2>&1 \
+      || { tail -20 $O/step_llama.log; exit 4; }
+    cat $O/step_llama3-8b-1l.txt
+    timeout -k 10 ${LIMIT:-300} python benchmarks/decode_step.py --skinny-gemm --model gpt2 --out $O/step_gpt2.txt > $O/step_gpt2.log 2>&1 \
+      || { tail -20 $O/step_gpt2.log; exit 5; }
+    cat $O/step_gpt2.txt
     ;;
   *)
     echo "unknown job $job"; exit 2
