@@ -1,6 +1,7 @@
 // In-kernel phase timing of one LDS-DMA GEMM config (diagnostic executable): compiles
 // csrc/kernels/gemm_glds_impl.h (configs 34, 13, 24, 27, 17, 45, 25, 22, and the wave-private
-// rings 120..123: W x S = 8 x 2, 4 x 3, 6 x 2, 12 x 1) into this translation unit
+// rings 120..123: W x S = 8 x 2, 4 x 3, 6 x 2, 12 x 1, and on 64-row tiles 130..133: 64 x 96 at
+// 4 x 2 and 3 x 2, 64 x 80 at 4 x 2 and 3 x 2, epilogues ln / lngelu only) into this translation unit
 // with DLS_STAMP recording s_memrealtime (100 MHz) per workgroup at: tile start, after the main
 // loop (1), after the K groups' fragments are summed or, on the one-pass configs (Cfg::ONE_PASS),
 // handed over through LDS (7), after the output image is in LDS (2; the one-pass finish has no
@@ -46,6 +47,18 @@ DLS_GLDS_DEFINE(25)
 DLS_GLDS_DEFINE(22)
 // splitk = 1 only: the split-K reduce launcher of the library is stubbed out below
 static bool launch_gemm_glds_local(const GemmArgs& a, int cfg, const float* colsum, int ln_mode) {
+  if (cfg >= kGemmPrivateWide) {
+    const int waves = cfg < kGemmPrivateWide + kGemmPrivateWideCount ? kGemmPrivateWideCfgs[cfg - kGemmPrivateWide].waves : 0;
+    if (!colsum || !private_wide_takes(waves, a, 1, ln_mode, false)) {
+      fprintf(stderr, "config %d does not take this shape / epilogue\n", cfg);
+      exit(2);
+    }
+    if (cfg == 130) launch_private_wide<64, 96, 4, 2>(a, colsum, ln_mode, 1e-5f, 0);
+    else if (cfg == 131) launch_private_wide<64, 96, 3, 2>(a, colsum, ln_mode, 1e-5f, 0);
+    else if (cfg == 132) launch_private_wide<64, 80, 4, 2>(a, colsum, ln_mode, 1e-5f, 0);
+    else launch_private_wide<64, 80, 3, 2>(a, colsum, ln_mode, 1e-5f, 0);
+    return false;
+  }
   if (cfg >= 120) {
     const int waves = cfg == 120 ? 8 : cfg == 121 ? 4 : cfg == 122 ? 6 : cfg == 123 ? 12 : 0;
     const bool ok = private_takes(waves, a, 1, ln_mode != 0, false);

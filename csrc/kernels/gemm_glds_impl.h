@@ -67,6 +67,15 @@ template <class T>
 __device__ __forceinline__ void consume_from_here(T& x) {
   asm volatile("" : "+v"(x));
 }
+// One output value of the one-pass finishes (glds_tile, gemm_private_wide_kernel) before RoPE and
+// rounding: x the K sum, b the bias, and with a folded norm (LNM) the row's rstd / mean and the
+// column's colsum(W') — W.LN(x) = rstd * (W' x - mu * colsum(W')) + (bias + W b), W' = W * ln_w
+// (host-derived) — else alpha.
+template <int ACT, bool LNM>
+__device__ __forceinline__ float finish_value(float x, float alpha, float rs, float mu, float cs, float b) {
+  if constexpr (LNM) return act_c<ACT>(rs * (x - mu * cs) + b);
+  else return act_c<ACT>(alpha * x + b);
+}
 template <bool WAIT_LDS_ONLY>
 __device__ __forceinline__ void epi_barrier() {
   if constexpr (WAIT_LDS_ONLY) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -947,9 +956,7 @@ __device__ __forceinline__ void glds_tile(bf16x8* smem, const bf16* __restrict__
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float x = e < 4 ? lo[e & 3] : hi[e & 3];
-            // W.LN(x) = rstd * (W' x - mu * colsum(W')) + (bias + W b), W' = W * ln_w (host-derived)
-            if constexpr (LNM) v[e] = act_c<ACT>(ln_rs1 * (x - ln_mu1 * csv[e]) + bv[e]);
-            else v[e] = act_c<ACT>(alpha * x + bv[e]);
+            v[e] = finish_value<ACT, LNM>(x, alpha, ln_rs1, ln_mu1, csv[e], bv[e]);
           }
           if constexpr (ROPE) {
             rope_pairs<4>(v, row, col, rope);
@@ -1802,18 +1809,22 @@ void grouped(const GemmArgs& a, int n_groups, const int* offsets, const unsigned
 // Every wave executes the same instruction counts whatever its slice holds, and no wave leaves
 // before the finish: the kernel's one barrier cannot be missed (the host refuses a K whose tiles
 // do not divide by W, and the grid is exactly the tile count — no idle block, no early return).
-template <int W_, int S_>
-struct PrivCfg {
-  static constexpr int W = W_, S = S_, BM = 32, BN = 48, BK = 64, CH = 8, FM = 2, FN = 3;
+// PrivTile is the family over its tile: PrivCfg<W, S> the 32 x 48 tiles of ids kGemmPrivate..,
+// 64 x 96 and 64 x 80 the folded-norm tiles of ids kGemmPrivateWide.. (gemm_private_wide_kernel).
+template <int BM_, int BN_, int W_, int S_>
+struct PrivTile {
+  static constexpr int W = W_, S = S_, BM = BM_, BN = BN_, BK = 64, CH = 8, FM = BM / 16, FN = BN / 16;
   static constexpr int T = 64 * W, PW = (BM + BN) / 8;  // DMA instructions per K-tile
   static constexpr int SLOT = (BM + BN) * CH;            // bf16x8 units of one K-tile image
   static constexpr int RING = S * SLOT, LDS_UNITS = W * RING;
   static constexpr int REG = FM * FN * 64;               // f32x4 records of a wave's fragments
+  static_assert(BM % 16 == 0 && BN % 16 == 0, "whole 16 x 16 fragments");
   static_assert(S >= 1 && PW * (S - 1) <= 63, "vmcnt range");
   static_assert(LDS_UNITS * 16 <= 163840 && T <= 1024, "LDS budget, block size");
   static_assert(REG <= RING, "a wave's fragment region lies inside its own ring");
-  static_assert(T >= BM * 8, "one 16-byte output segment per storing thread");
 };
+template <int W_, int S_>
+using PrivCfg = PrivTile<32, 48, W_, S_>;
 
 template <class P>
 __device__ __forceinline__ void mainloop_private(bf16x8* ring, const bf16* __restrict__ A, int lda,
@@ -1888,6 +1899,7 @@ __global__ __launch_bounds__(P::T, 1) void gemm_private_kernel(const bf16* __res
                                                                const bf16* __restrict__ R, int ldr,
                                                                float* __restrict__ stats_out, int M, int N, int K,
                                                                float alpha, int tiles_m) {
+  static_assert(P::T >= P::BM * 8, "one 16-byte output segment per storing thread");
   __shared__ bf16x8 smem[P::LDS_UNITS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2048,6 +2060,212 @@ void launch_private(const GemmArgs& a, hipStream_t s) {
                      a.K, a.alpha, tiles_m)
   // (the output stores' cache policy, GemmArgs::stream_pol bits 1 and 2, as launch<C> maps them:
   // policy stores carry 32-bit byte offsets, outputs of 2 GB and more keep the default stores)
+  switch ((size_t)a.M * a.ldc * 2 < (1ull << 31) ? a.stream_pol & 7 : 0) {
+    case 2: case 3: DLS_PK(kPolStream); break;
+    case 4: case 5: DLS_PK(kPolWT); break;
+    default: DLS_PK(0);
+  }
+#undef DLS_PK
+}
+
+// ---- Wave-private rings, 64-row tiles with the folded-norm finish (kGemmPrivateWide ids) ----
+//
+// C = act(rstd * (A @ W'^T - mu * colsum(W')) + bias): what GPT-2's QKV and fc1 attach — a folded
+// norm (either mode) whose row statistics come from ext_stats, bias, no activation or GeLU. The K
+// loop is mainloop_private on a 64 x 96 or 64 x 80 tile (one tile per CU at 512 x 3072 and
+// 512 x 2304: a whole round); the finish is the one above with more segments than threads: every
+// wave writes its FM * FN fragments into a region at the start of its own ring, ONE barrier, and
+// the threads walk the tile's 16-byte segments in T-wide passes, each summing the W records of
+// its segment in ascending wave order and finishing it with finish_value. A pass maps 16
+// consecutive threads to 4 consecutive chunks of 4 consecutive rows (the conflict-free read of
+// glds_tile's record layout); BN = 80 leaves the last quad of chunks half empty. All operands of
+// all passes are requested in one batch behind the wave's last vmcnt wait.
+template <class P, int SPOL>
+__global__ __launch_bounds__(P::T, 1) void gemm_private_wide_kernel(const bf16* __restrict__ A,
+                                                                    const bf16* __restrict__ W, bf16* __restrict__ Cp,
+                                                                    const bf16* __restrict__ bias,
+                                                                    const float* __restrict__ ln_colsum,
+                                                                    const float* __restrict__ ext_stats, int lda,
+                                                                    int ldw, int ldc, int M, int N, int K, int tiles_m,
+                                                                    int ln_mode, int act, float ln_eps) {
+  constexpr int BNC = P::BN / 8, NQ = (BNC + 3) / 4;  // 16-byte chunks of a tile row, quads of them
+  constexpr int SEGS = P::BM * NQ * 4, NPASS = SEGS / P::T;
+  static_assert(SEGS % P::T == 0, "whole passes: no thread without a segment");
+  __shared__ bf16x8 smem[P::LDS_UNITS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int m0 = (tile % tiles_m) * P::BM, n0 = (tile / tiles_m) * P::BN;
+  DLS_STAMP(0)
+  const int nk = K / (P::BK * P::W);  // K-tiles of every wave's slice
+  bf16x8* ring = smem + wave * P::RING;
+  f32x4 acc[P::FM][P::FN];
+#pragma unroll
+  for (int i = 0; i < P::FM; ++i)
+#pragma unroll
+    for (int j = 0; j < P::FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  mainloop_private<P>(ring, A, lda, W, ldw, M, N, m0, n0, wave * nk * P::BK, nk, lane, acc);
+  DLS_STAMP(1)
+  // pass p: segment q = tid + p T -> chunk 4 (q / 16 % NQ) + q % 4 of tile row 4 (q / 16 / NQ) + q / 4 % 4
+  auto seg_row = [&](int p) { const int q = tid + p * P::T; return (q >> 4) / NQ * 4 + ((q >> 2) & 3); };
+  auto seg_chunk = [&](int p) { const int q = tid + p * P::T; return (q >> 4) % NQ * 4 + (q & 3); };
+  // (range-checked buffer loads: rows past M and, with the vector forms, columns past N read zeros;
+  // a bias / colsum that is not aligned, or N % 4 != 0, is read in place behind the barrier)
+  const bool pre_bvec = ((reinterpret_cast<uintptr_t>(bias) & 7) | (N & 3)) == 0;
+  const bool pre_cvec = ((reinterpret_cast<uintptr_t>(ln_colsum) & 15) | (N & 3)) == 0;
+  const bool v16 = ((reinterpret_cast<uintptr_t>(Cp) | ((uintptr_t)ldc * 2)) & 15) == 0;
+  u32x2 o_st[NPASS];     // fp32 bits of the row's (sum, sum of squares)
+  u32x2 o_bv[NPASS][2];  // pre_bvec: 4 bf16 each
+  u32x4 o_cs[NPASS][2];  // pre_cvec: fp32 bits
+  {
+    constexpr int kRaw = 0x00020000;  // raw buffer, 32-bit data
+    const auto rst = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ext_stats), 0, M * 8, kRaw);
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) o_st[p] = __builtin_amdgcn_raw_buffer_load_b64(rst, (m0 + seg_row(p)) * 8, 0, 0);
+    if (bias && pre_bvec) {
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(bias), 0, N * 2, kRaw);
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          o_bv[p][h] = __builtin_amdgcn_raw_buffer_load_b64(rs, (n0 + seg_chunk(p) * 8) * 2 + h * 8, 0, 0);
+    }
+    if (pre_cvec) {
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ln_colsum), 0, N * 4, kRaw);
+#pragma unroll
+      for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          o_cs[p][h] = __builtin_amdgcn_raw_buffer_load_b128(rs, (n0 + seg_chunk(p) * 8) * 4 + h * 16, 0, 0);
+    }
+  }
+  // fragment records: glds_tile's one-pass layout with one wave per region (NW = 1)
+  f32x4* reg = reinterpret_cast<f32x4*>(ring);
+#pragma unroll
+  for (int i = 0; i < P::FM; ++i)
+#pragma unroll
+    for (int j = 0; j < P::FN; ++j) {
+      const int cl = j * 16 + (lane >> 4) * 4;
+      reg[(i * P::FN + j) * 64 + (lane & 48) + ((lane & 15) ^ (((cl >> 3) & 3) << 2))] = acc[i][j];
+    }
+  epi_barrier<true>();  // THE barrier: every wave's fragments are in LDS (operand requests stay in flight)
+  DLS_STAMP(7)
+  // Three phases, so that the sums and the values are straight-line code: (1) every pass's W
+  // records summed in ascending wave order; (2) every pass's operands decoded (the in-place reads
+  // of an unaligned bias / colsum branch here); (3) every value; then (below) every store —
+  // vmcnt counts stores too, so a store between two passes would turn the next pass's wait for
+  // its (long landed) operands into a wait for that store's round trip.
+  const f32x4* red = reinterpret_cast<const f32x4*>(smem);
+  f32x4 lo[NPASS], hi[NPASS];
+#pragma unroll
+  for (int p = 0; p < NPASS; ++p) {
+    const int rl = seg_row(p);
+    // (chunks past BNC read chunk BNC - 1 again and store nothing)
+    const int ccr = min(seg_chunk(p), BNC - 1), cl0 = ccr * 8;
+    const int rec = ((rl / 16) * P::FN + cl0 / 16) * 64 + (cl0 & 8) * 4 + ((rl & 15) ^ ((ccr & 3) << 2));
+    f32x4 part_lo[P::W], part_hi[P::W];
+#pragma unroll
+    for (int w = 0; w < P::W; ++w) {
+      part_lo[w] = red[w * P::RING + rec];
+      part_hi[w] = red[w * P::RING + rec + 16];
+    }
+    lo[p] = part_lo[0], hi[p] = part_hi[0];
+#pragma unroll
+    for (int w = 1; w < P::W; ++w) {
+      lo[p] += part_lo[w];
+      hi[p] += part_hi[w];
+    }
+  }
+  const float inv_k = 1.0f / (float)K;
+  float rs[NPASS], mu[NPASS], bv[NPASS][8], csv[NPASS][8];
+#pragma unroll
+  for (int p = 0; p < NPASS; ++p) {
+    const int col = n0 + seg_chunk(p) * 8;
+    consume_from_here(o_st[p]);
+    const float a = __uint_as_float(o_st[p][0]), q = __uint_as_float(o_st[p][1]);
+    mu[p] = ln_mode == 1 ? a * inv_k : 0.f;
+    rs[p] = rsqrtf(fmaxf(q * inv_k - mu[p] * mu[p], 0.f) + ln_eps);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bv[p][e] = csv[p][e] = 0.f;
+    if (bias) {
+      if (pre_bvec) {
+        uint32_t w[8];  // (a bf16 is the high half of its fp32)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          consume_from_here(o_bv[p][h]);
+          const uint32_t p0 = o_bv[p][h][0], p1 = o_bv[p][h][1];
+          w[4 * h + 0] = p0 << 16;
+          w[4 * h + 1] = p0 & 0xffff0000u;
+          w[4 * h + 2] = p1 << 16;
+          w[4 * h + 3] = p1 & 0xffff0000u;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bv[p][e] = col + e < N ? __uint_as_float(w[e]) : 0.f;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < N) bv[p][e] = bf2f(bias[col + e]);
+      }
+    }
+    if (pre_cvec) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) consume_from_here(o_cs[p][h]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) csv[p][e] = col + e < N ? __uint_as_float(o_cs[p][e >> 2][e & 3]) : 0.f;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (col + e < N) csv[p][e] = ln_colsum[col + e];
+    }
+  }
+  bf16x8 seg[NPASS];
+  auto finish = [&](auto act_tag) {
+    constexpr int ACT = decltype(act_tag)::value;
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        seg[p][e] = f2bf(finish_value<ACT, true>(e < 4 ? lo[p][e & 3] : hi[p][e & 3], 1.f, rs[p], mu[p], csv[p][e],
+                                                 bv[p][e]));
+  };
+  if (act == ACT_GELU_TANH) finish(std::integral_constant<int, ACT_GELU_TANH>{});
+  else finish(std::integral_constant<int, ACT_NONE>{});
+#pragma unroll
+  for (int p = 0; p < NPASS; ++p) {
+    const int cc = seg_chunk(p), row = m0 + seg_row(p), col = n0 + cc * 8;
+    if (cc < BNC && row < M && col < N) {
+      if (v16 && col + 8 <= N) {
+        store16_pol<SPOL>(Cp, ((size_t)row * ldc + col) * 2, *reinterpret_cast<const u32x4*>(&seg[p]));
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < N) Cp[(size_t)row * ldc + col + e] = seg[p][e];
+      }
+    }
+  }
+  DLS_STAMP(3)
+}
+
+// Whether the 64-row wave-private family takes this launch: the whole K in one block with
+// K % (64 W) == 0, a folded norm whose row statistics come from ext_stats, bias, no activation or
+// GeLU — no RoPE, SwiGLU, split-K, row range, residual or stats_out (the callers fall back to the
+// table's previous config, or refuse a forced id).
+inline bool private_wide_takes(int waves, const GemmArgs& a, int splitk, int ln_mode, bool ranged) {
+  return waves > 0 && a.K > 0 && a.K % (64 * waves) == 0 && splitk <= 1 && (ln_mode == 1 || ln_mode == 2) &&
+         a.ext_stats && !ranged && (a.act == ACT_NONE || a.act == ACT_GELU_TANH) && a.rope.cols == 0 && !a.R &&
+         !a.stats_out;
+}
+
+template <int BM_, int BN_, int W_, int S_>
+void launch_private_wide(const GemmArgs& a, const float* ln_colsum, int ln_mode, float ln_eps, hipStream_t s) {
+  using P = PrivTile<BM_, BN_, W_, S_>;
+  const int tiles_m = (a.M + P::BM - 1) / P::BM, tiles_n = (a.N + P::BN - 1) / P::BN;
+  dim3 grid(tiles_m * tiles_n), block(P::T);
+#define DLS_PK(POL_)                                                                                              \
+  hipLaunchKernelGGL((gemm_private_wide_kernel<P, POL_>), grid, block, 0, s, (const bf16*)a.A, (const bf16*)a.W, \
+                     (bf16*)a.C, (const bf16*)a.bias, ln_colsum, a.ext_stats, a.lda, a.ldw, a.ldc, a.M, a.N, a.K, \
+                     tiles_m, ln_mode, a.act, ln_eps)
+  // (the output stores' cache policy as launch_private maps it)
   switch ((size_t)a.M * a.ldc * 2 < (1ull << 31) ? a.stream_pol & 7 : 0) {
     case 2: case 3: DLS_PK(kPolStream); break;
     case 4: case 5: DLS_PK(kPolWT); break;

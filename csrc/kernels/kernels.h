@@ -111,6 +111,21 @@ constexpr int kGemmPrivate = 120, kGemmPrivateCount = 4;
 int gemm_private_waves(int cfg);  // W of a family id, 0 for any other id
 bool gemm_private_takes(const GemmArgs& a, int cfg, int splitk, bool folded_norm, bool ranged);
 bool launch_gemm_private(const GemmArgs& a, int cfg, hipStream_t s);
+// The same rings on 64-row tiles with the folded-norm finish (gemm_private_wide_kernel), ids
+// kGemmPrivateWide + i: one tile per CU at GPT-2's fc1 (512 x 3072 on 64 x 96) and QKV (512 x 2304
+// on 64 x 80). It takes folded-norm launches whose row statistics come from ext_stats — the whole
+// K in one block with K % (64 W) == 0, bias, no activation or GeLU; no RoPE, SwiGLU, split-K, row
+// range, residual or stats_out (gemm_private_wide_takes; the launcher launches nothing and returns
+// false otherwise).
+constexpr int kGemmPrivateWide = 130, kGemmPrivateWideCount = 4;
+struct GemmPrivateWideCfg {
+  int bm, bn, waves, slots;  // tile, W waves x S ring slots
+};
+constexpr GemmPrivateWideCfg kGemmPrivateWideCfgs[kGemmPrivateWideCount] = {{64, 96, 4, 2}, {64, 96, 3, 2}, {64, 80, 4, 2}, {64, 80, 3, 2}};
+int gemm_private_wide_waves(int cfg);  // W of a family id, 0 for any other id
+bool gemm_private_wide_takes(const GemmArgs& a, int cfg, int splitk, int ln_mode, bool ranged);
+bool launch_gemm_private_wide(const GemmArgs& a, int cfg, const float* ln_colsum, int ln_mode, float ln_eps,
+                              hipStream_t s);
 
 // Grouped MoE-expert GEMM: E groups in ONE launch (grid = E x column tiles). Group g multiplies
 // rows [offsets[g], offsets[g+1]) of A by its own weight (w_ptrs[g], [N][K], ldw = a.ldw) and

@@ -95,10 +95,12 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 double norm_eps, int64_t stream_pol) {
   check_bf16(a_in, "A");
   check_bf16(w, "W");
+  const bool wide = gemm_private_wide_waves((int)config) != 0;  // (64-row tiles, folded-norm finish)
   const bool priv = gemm_private_waves((int)config) != 0;
-  TORCH_CHECK(config < kRegStage + 4 || priv, "unknown GEMM config ", config, " (register-staged configs are ",
-              kRegStage, "..", kRegStage + 3, ", wave-private rings ", kGemmPrivate, "..",
-              kGemmPrivate + kGemmPrivateCount - 1, ")");
+  TORCH_CHECK(config < kRegStage + 4 || priv || wide, "unknown GEMM config ", config,
+              " (register-staged configs are ", kRegStage, "..", kRegStage + 3, ", wave-private rings ", kGemmPrivate,
+              "..", kGemmPrivate + kGemmPrivateCount - 1, " and ", kGemmPrivateWide, "..",
+              kGemmPrivateWide + kGemmPrivateWideCount - 1, ")");
   at::Tensor a = as2d(a_in);
   check_rows(a, "A");
   check_rows(w, "W");
@@ -203,7 +205,7 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 "RoPE epilogue: D % 4 == 0, whole heads, LDS-DMA kernel, no activation / SwiGLU / row range");
     g.rope = RopeArgs{rope_cos->data_ptr<float>(), rope_sin->data_ptr<float>(), (int)rope_S, (int)rope_D,
                       (int)rope_cols};
-    if (config >= kRegStage && !priv) config = -1;
+    if (config >= kRegStage && !priv && !wide) config = -1;
   }
   const bool glds_ok = (K % 64 == 0);
   const float* csp = nullptr;
@@ -220,6 +222,17 @@ at::Tensor gemm(const at::Tensor& a_in, const at::Tensor& w, const c10::optional
                 " waves) takes plain launches only: K % ", 64 * gemm_private_waves((int)config),
                 " == 0, no activation, folded norm, RoPE, SwiGLU, split-K or row range");
     TORCH_CHECK(launch_gemm_private(g, (int)config, cur_stream()), "GEMM config ", config, " refused the launch");
+    post_norm(false);
+    return c;
+  }
+  if (wide) {
+    TORCH_CHECK(!compact_rows && gemm_private_wide_takes(g, (int)config, (int)splitk, (int)ln_mode, rowp != nullptr),
+                "GEMM config ", config, " (wave-private rings on 64-row tiles, ", gemm_private_wide_waves((int)config),
+                " waves) takes folded-norm launches with ext_stats only: K % ",
+                64 * gemm_private_wide_waves((int)config),
+                " == 0, no activation or GeLU, no RoPE, SwiGLU, split-K, row range, residual or stats_out");
+    TORCH_CHECK(launch_gemm_private_wide(g, (int)config, csp, (int)ln_mode, (float)ln_eps, cur_stream()),
+                "GEMM config ", config, " refused the launch");
     post_norm(false);
     return c;
   }
@@ -1833,6 +1846,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("PRIVATE") = kGemmPrivate;
   m.attr("PRIVATE_COUNT") = kGemmPrivateCount;
   m.def("gemm_private_waves", &gemm_private_waves);
+  m.attr("PRIVATE_WIDE") = kGemmPrivateWide;
+  m.attr("PRIVATE_WIDE_COUNT") = kGemmPrivateWideCount;
+  m.def("gemm_private_wide_cfg", [](int64_t cfg) {  // (bm, bn, waves, slots) of a family id
+    TORCH_CHECK(gemm_private_wide_waves((int)cfg) != 0, "GEMM config ", cfg, " is not a 64-row wave-private id");
+    const GemmPrivateWideCfg& w = kGemmPrivateWideCfgs[cfg - kGemmPrivateWide];
+    return std::make_tuple(w.bm, w.bn, w.waves, w.slots);
+  });
   m.def("gemm_pick_config", &gemm_pick_config);
   m.def("gemm_glds_num_configs", &gemm_glds_num_configs);
   m.def("gemm_glds_kstep", &gemm_glds_kstep);

@@ -287,6 +287,8 @@ def linear(x, w, bias=None, act=None, residual=None, alpha=1.0, out=None, rows=N
             cfg, sk = tuning.lookup_fused(rows_hint or M, w.shape[0], w.shape[1], tuning.tag(a, rows is not None))
         # (a wave-private choice the family refuses for this epilogue: the same tile's K-grouped config)
         cfg, sk = tuning.resolve_private((cfg, sk), w.shape[1], a, rows is not None, rope is not None)
+        # (the 64-row family takes folded-norm launches only: what the table held before)
+        cfg, sk = tuning.resolve_private_wide((cfg, sk), w.shape[1], a, rows is not None, rope is not None)
         rc, rs_, rS, rD, rcols = rope if rope is not None else (None, None, 1, 2, 0)
         y = ext().gemm(x, w, bias, residual, a, float(alpha), out, cfg, sk, None, 0, 1e-5, rows, bool(compact),
                        rc, rs_, int(rS), int(rD), int(rcols), stats_out, None,
@@ -584,6 +586,9 @@ def linear_norm(x, w_derived, colsum, bias_derived, mode, eps=1e-5, act=None, re
                        stream_pol=pol)
         return out
     cfg, sk = tuning.resolve_private(tuning.lookup_fused(M, N, K, tuning.tag(a)), K, a, folded=True)
+    # a 64-row wave-private id goes through when that family takes the launch, else its fallback
+    cfg, sk = tuning.resolve_private_wide((cfg, sk), K, a, rope=rope is not None, folded=True,
+                                          ext_stats=ext_stats is not None, residual=residual is not None)
     if ext_stats is None:
         sk = 1
         if 0 <= cfg < tuning.REGSTAGE and tuning.kstep(cfg) != 64:
@@ -593,7 +598,9 @@ def linear_norm(x, w_derived, colsum, bias_derived, mode, eps=1e-5, act=None, re
                         if 0 <= c < tuning.REGSTAGE and tuning.kstep(c) == 64), -1)
     rc, rs_, rS, rD, rcols = rope if rope is not None else (None, None, 1, 2, 0)
     pol = _stream_pol(N, K)
-    y = ext().gemm(x, w_derived, bias_derived, residual, a, 1.0, out, cfg if cfg < tuning.REGSTAGE else -1, sk, colsum,
+    if cfg >= tuning.REGSTAGE and cfg not in tuning.PRIVATE_WIDE_CFGS:
+        cfg = -1  # (register-staged choices have no folded norm: the kernel heuristic)
+    y = ext().gemm(x, w_derived, bias_derived, residual, a, 1.0, out, cfg, sk, colsum,
                    m, float(eps), None, False, rc, rs_, int(rS), int(rD), int(rcols), None, ext_stats,
                    stream_pol=pol)
     return y.view(shp) if out is None else out

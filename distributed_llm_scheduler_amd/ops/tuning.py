@@ -67,6 +67,39 @@ def resolve_private(choice: Tuple[int, int], K: int, act: int = 0, ranged: bool 
     return (cfg, 1) if private_takes(cfg, K, sk, act, ranged, rope, folded) else PRIVATE_FALLBACK
 
 
+# The same rings on 64-row tiles with the folded-norm finish (csrc kernels.h kGemmPrivateWide): id ->
+# (BM, BN, waves W, ring slots S). The family takes folded-norm launches whose row statistics come
+# from ext_stats (private_wide_takes); a table entry naming it runs PRIVATE_WIDE_FALLBACK — the
+# 64 x 64 K-grouped config the table held before — for every other launch of the shape.
+PRIVATE_WIDE = 130
+PRIVATE_WIDE_CFGS = {130: (64, 96, 4, 2), 131: (64, 96, 3, 2), 132: (64, 80, 4, 2), 133: (64, 80, 3, 2)}
+PRIVATE_WIDE_FALLBACK = (17, 1)
+
+
+def private_wide_takes(cfg: int, K: int, sk: int = 1, act: int = 0, ranged: bool = False, rope: bool = False,
+                       folded: bool = False, ext_stats: bool = False, residual: bool = False,
+                       stats_out: bool = False) -> bool:
+    """Does 64-row wave-private config ``cfg`` take this launch (csrc gemm_private_wide_takes)? Every
+    wave owns K / W whole 64-deep K-tiles; a folded norm with handed-over row statistics, bias and
+    no activation or GeLU (act 0 / 1) are all it attaches."""
+    w = PRIVATE_WIDE_CFGS.get(cfg, (0, 0, 0, 0))[2]
+    return (w > 0 and K > 0 and K % (64 * w) == 0 and sk <= 1 and act in (0, 1) and folded and ext_stats
+            and not (ranged or rope or residual or stats_out))
+
+
+def resolve_private_wide(choice: Tuple[int, int], K: int, act: int = 0, ranged: bool = False, rope: bool = False,
+                         folded: bool = False, ext_stats: bool = False, residual: bool = False,
+                         stats_out: bool = False) -> Tuple[int, int]:
+    """A tuned choice as it is launched: a 64-row wave-private id stays if the family takes the
+    launch, else PRIVATE_WIDE_FALLBACK; any other choice is returned as it is."""
+    cfg, sk = choice
+    if cfg not in PRIVATE_WIDE_CFGS:
+        return choice
+    if private_wide_takes(cfg, K, sk, act, ranged, rope, folded, ext_stats, residual, stats_out):
+        return (cfg, 1)
+    return PRIVATE_WIDE_FALLBACK
+
+
 def _key(M: int, N: int, K: int, tg: str = "") -> str:
     return f"{M}x{N}x{K}{tg}"
 

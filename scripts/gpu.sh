@@ -143,6 +143,12 @@ case "$job" in
         timeout -k 5 30 gpubin/gemm_stamps ${s[0]} ${s[1]} ${s[2]} ${s[3]} $mode >> $O/stamps.txt 2>&1 || { echo "FAILED $shape $mode"; exit 3; }
       done
     done
+    # the 64-row wave-private rings (130 / 131: 64 x 96 at W x S = 4 x 2 / 3 x 2; 132 / 133: 64 x 80),
+    # which take the step's folded-norm operands only, beside config 17 above
+    for shape in "130 512 3072 768 lngelu" "131 512 3072 768 lngelu" "132 512 3072 768 lngelu" "133 512 3072 768 lngelu" \
+                 "130 512 2304 768 ln" "131 512 2304 768 ln" "132 512 2304 768 ln" "133 512 2304 768 ln"; do
+      timeout -k 5 30 gpubin/gemm_stamps $shape >> $O/stamps.txt 2>&1 || { echo "FAILED $shape"; exit 3; }
+    done
     cat $O/stamps.txt
     ;;
   prefill)
