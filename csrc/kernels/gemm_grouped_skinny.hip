@@ -25,7 +25,7 @@
 // launch follows whatever routing the device holds at replay. A group of more than 16 rows takes
 // further 16-row passes over the same weights (correct, not fast).
 //
-// Operand layout. Operands are swapped as in gemm_w8_grouped.hip and attn_decode.hip: the weight
+// Operand layout. Operands are swapped as in gemm_w8_grouped.hip and attn_decode_impl.h: the weight
 // rows are the MFMA's A operand (lane l16 = weight row), the <= 16 token rows its B operand
 // (lane l16 = token), so a lane's four accumulator values are four CONSECUTIVE output columns of
 // one token row — one 8-byte store — and a gate/up pair is two fragments of the same lane. The

@@ -379,7 +379,8 @@ struct AttnArgs {
 void launch_attention_fwd(const AttnArgs& a, hipStream_t s);
 void attention_split_sizes(const AttnArgs& a, size_t* part_floats, size_t* counters);
 
-// KV cache and decode steps (attn_decode.hip, attn_decode_fp8.hip). The caches are bf16
+// KV cache and decode steps (attn_decode.hip, attn_decode_fp8.hip; the decode-attention kernel of
+// both is the one template of attn_decode_impl.h). The caches are bf16
 // [B][C][n_kv_head*D], or with kv_fp8 e4m3 bytes of that shape plus fp32 power-of-two scales
 // [B][n_kv_head][C], one per (position, KV head); pos is int32 [B] in device memory (the length of
 // every sequence before the step), so one captured launch serves every step.

@@ -8,7 +8,7 @@
 // index, and for sampling rows a histogram of the keys' high bytes (integer LDS atomics). With
 // more than one slice the workgroup publishes both write-through (sc1), draws an agent-scope
 // ticket of its row, and the last arriver reloads all slices (sc1 loads, its own included) and
-// merges them: the pattern of attn_decode.hip; the last arriver resets the ticket, so the
+// merges them: the pattern of attn_decode_impl.h; the last arriver resets the ticket, so the
 // workspace needs zeroing once. Greedy rows end here: one pass over the logits.
 //
 // Phase 2, the last arriver alone, the row now in L2 / the Infinity Cache: top-k by two 8-bit

@@ -940,7 +940,7 @@ def ref_attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_di
 def attention_decode(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None, out=None,
                      workspace=None, chunk=0, k_scale=None, v_scale=None):
     """Causal attention of the T new queries of every sequence (q [B*T][>= n_head*head_dim])
-    against its cache rows ``0 .. pos[b]+t``; runs after ``kv_append``. GPU: attn_decode.hip with
+    against its cache rows ``0 .. pos[b]+t``; runs after ``kv_append``. GPU: attn_decode_impl.h with
     ``workspace`` from ``attention_decode_workspace`` (``chunk``: keys per workgroup, 0 = the
     launcher's choice; the workspace must be sized with the same value). CPU: fp32 torch. With
     ``k_scale`` / ``v_scale`` the caches are fp8 (attn_decode_fp8.hip; the workspace is the same);

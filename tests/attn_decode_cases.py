@@ -5,7 +5,7 @@ process.
 A case is a step: caches [B][C][nkv*D] holding ``pos[b]`` rows per sequence (every other row is
 stale), and T new tokens per sequence as a packed qkv buffer. The step appends the new K and V
 rows at ``pos[b] .. pos[b]+T-1`` and attends query t of sequence b to cache rows ``0 .. pos[b]+t``.
-The kernel (csrc/kernels/attn_decode.hip) gives one workgroup one chunk of KC keys of one
+The kernel (csrc/kernels/attn_decode_impl.h) gives one workgroup one chunk of KC keys of one
 (sequence, KV head) and merges the chunks that hold keys by tickets. The capacity is C = 640 and
 the tests pass chunk = 128, so these small caches span five chunks; at D = 64 a 128-key chunk is
 half of the kernel's 256-key stage, at D = 128 a whole one.
