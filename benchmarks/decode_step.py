@@ -8,7 +8,7 @@ microsecond of event overhead) — for T new tokens per step from a context of P
 share of the step is the baseline a GEMV path would be measured against.
 
     python benchmarks/decode_step.py [--model llama3-8b-1l] [--kv-cache 8192] [--kv-dtype fp8] [--only B,T,past]
-                                     [--out FILE] [--generate] [--skinny-gemm [--max-rows N]]
+                                     [--out FILE] [--generate] [--skinny-gemm | --skinny-w8 [--max-rows N]]
 
 --kv-dtype fp8: the caches hold e4m3 bytes and per-(position, KV head) scales (runtime.plan kv_dtype).
 --generate: instead of the breakdown, the T = 1 cases with and without on-device sampling
@@ -21,6 +21,10 @@ steps, the medians, the ratio and in how many rounds the step with the option wa
 default cases are then SKINNY_CASES (llama3-8b-1l) or GPT2_SKINNY_CASES (--model gpt2). --max-rows N
 sets ops.SKINNY_MAX_ROWS for the run (a bound search; the default measures what the executor does),
 --lm-head 0/1 ops.SKINNY_LMHEAD.
+
+--skinny-w8: the same protocol for fp8-weight plans (weight_dtype="fp8"): the plan with skinny_w8=True against
+the plan without it, whose GEMMs run on the tiles of ops.linear_w8. --max-rows N then sets
+ops.SKINNY_W8_MAX_ROWS; DLS_SKINNY=all in the environment takes every step of up to 16 rows (the bound search).
 
 Needs a GPU.
 """
@@ -40,6 +44,9 @@ from distributed_llm_scheduler_amd.parallel import runtime  # noqa: E402
 CASES = [(1, 1, 512), (1, 1, 8000), (1, 16, 8000), (8, 1, 8000)]  # (batch, T, past)
 SKINNY_CASES = [(1, 1, 512), (1, 1, 8000), (2, 1, 8000), (4, 1, 8000), (8, 1, 8000), (16, 1, 8000), (1, 16, 8000)]
 GPT2_SKINNY_CASES = [(1, 1, 512), (8, 1, 1000)]
+# --skinny-w8: the row-bound search of ops.SKINNY_W8_MAX_ROWS (GPT-2 has 1024 positions: its long context is 1000)
+SKINNY_W8_CASES = [(1, 1, 512)] + [(b, 1, 8000) for b in (1, 2, 4, 8, 16)]
+GPT2_SKINNY_W8_CASES = [(1, 1, 512)] + [(b, 1, 1000) for b in (1, 2, 4, 8, 16)]
 
 
 def one(model, C, B, T, past, steps=10, rounds=5, kv_dtype="bf16"):
@@ -132,16 +139,18 @@ def generate_delta(model, C, B, past, kv_dtype="bf16", steps=10, rounds=5):
     return [line]
 
 
-def skinny_delta(model, C, B, T, past, kv_dtype="bf16", steps=10, rounds=5):
-    """us per captured step of the plan without and with skinny_gemm=True, the two graphs alternating."""
+def skinny_delta(model, C, B, T, past, kv_dtype="bf16", steps=10, rounds=5, option="skinny_gemm"):
+    """us per captured step of the plan without and with ``option`` (skinny_gemm, or skinny_w8 on an
+    fp8-weight plan), the two graphs alternating."""
     from distributed_llm_scheduler_amd import ops
 
     dev = torch.device("cuda:0")
     moe = bool(registry.get_config(model).n_experts)
     exs, store = {}, None
+    wd = dict(weight_dtype="fp8") if option == "skinny_w8" else {}
     for what, flag in (("tiles", False), ("skinny", True)):
-        p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype, moe_decode=moe,
-                         **(dict(skinny_gemm=True) if flag else {}))
+        p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, kv_dtype=kv_dtype, moe_decode=moe, **wd,
+                         **({option: True} if flag else {}))
         store = store or runtime.make_store(p, device_init=runtime.device_init_ok(p, 0))
         ex = runtime.make_executor(p, 0, dev, store)
         ex.kv_randomize(past)
@@ -171,12 +180,14 @@ def skinny_delta(model, C, B, T, past, kv_dtype="bf16", steps=10, rounds=5):
             t[what].append(timed(exs[what]))
     med = {k: statistics.median(v) for k, v in t.items()}
     wins = sum(a < b for a, b in zip(t["skinny"], t["tiles"]))
-    line = (f"{model}  B {B}  T {T}  past {past}  cache {C} ({kv_dtype}): {med['tiles']:.1f} us per step on the tiles "
+    line = (f"{model}{' fp8 weights' if wd else ''}  B {B}  T {T}  past {past}  cache {C} ({kv_dtype}): "
+            f"{med['tiles']:.1f} us per step on the tiles "
             f"({exs['tiles'].launches} launches; min {min(t['tiles']):.1f}, max {max(t['tiles']):.1f}), "
-            f"{med['skinny']:.1f} us with skinny_gemm ({exs['skinny'].launches} launches; min {min(t['skinny']):.1f}, "
+            f"{med['skinny']:.1f} us with {option} ({exs['skinny'].launches} launches; min {min(t['skinny']):.1f}, "
             f"max {max(t['skinny']):.1f}): {med['tiles'] / med['skinny']:.3f}x, faster in {wins} of {rounds} rounds; "
             f"{len(ran)} GEMMs skinny (stream={exs['skinny']._skinny_stream}), fallbacks: {fell or 'none'}; "
-            f"SKINNY_MAX_ROWS {ops.SKINNY_MAX_ROWS}, SKINNY_LMHEAD {ops.SKINNY_LMHEAD}; medians of {rounds} alternating "
+            f"SKINNY_MAX_ROWS {ops.SKINNY_MAX_ROWS}, SKINNY_W8_MAX_ROWS {ops.SKINNY_W8_MAX_ROWS}, SKINNY_LMHEAD "
+            f"{ops.SKINNY_LMHEAD}, DLS_SKINNY {os.environ.get('DLS_SKINNY', 'unset')}; medians of {rounds} alternating "
             f"rounds of {steps} steps")
     del exs, store
     torch.cuda.empty_cache()
@@ -201,25 +212,32 @@ def main():
                     help="the T = 1 cases with and without on-device sampling, alternating, and the difference")
     ap.add_argument("--skinny-gemm", action="store_true",
                     help="every case with and without the plan option skinny_gemm, the captured steps alternating")
-    ap.add_argument("--max-rows", type=int, default=None, help="with --skinny-gemm: ops.SKINNY_MAX_ROWS for this run")
+    ap.add_argument("--skinny-w8", action="store_true",
+                    help="every case of the fp8-weight plan with and without the plan option skinny_w8, alternating")
+    ap.add_argument("--max-rows", type=int, default=None,
+                    help="with --skinny-gemm: ops.SKINNY_MAX_ROWS for this run (--skinny-w8: ops.SKINNY_W8_MAX_ROWS)")
     ap.add_argument("--lm-head", type=int, default=None, help="with --skinny-gemm: ops.SKINNY_LMHEAD for this run (0 / 1)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("decode_step.py needs a GPU")
     cases = [tuple(int(x) for x in a.only.split(","))] if a.only else CASES
-    if a.skinny_gemm:
+    if a.skinny_gemm or a.skinny_w8:
         from distributed_llm_scheduler_amd import ops
 
-        if a.max_rows is not None:
-            ops.SKINNY_MAX_ROWS = a.max_rows  # (read by the executor at every launch)
+        if a.max_rows is not None and a.skinny_w8:
+            ops.SKINNY_W8_MAX_ROWS = a.max_rows  # (read when the executor is made)
+        elif a.max_rows is not None:
+            ops.SKINNY_MAX_ROWS = a.max_rows  # (read when the executor is made)
         if a.lm_head is not None:
             ops.SKINNY_LMHEAD = bool(a.lm_head)
         if not a.only:
             cases = GPT2_SKINNY_CASES if a.model.startswith("gpt2") else SKINNY_CASES
+            if a.skinny_w8:
+                cases = GPT2_SKINNY_W8_CASES if a.model.startswith("gpt2") else SKINNY_W8_CASES
         lines = []
         for B, T, past in cases:
             lines += skinny_delta(a.model, min(a.kv_cache, registry.get_config(a.model).n_positions), B, T, past,
-                                  a.kv_dtype)
+                                  a.kv_dtype, option="skinny_w8" if a.skinny_w8 else "skinny_gemm")
             print(lines[-1], flush=True)
     elif a.generate:
         lines = []

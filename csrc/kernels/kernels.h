@@ -223,6 +223,34 @@ int gemm_w8_max_splitk(int cfg, int K);
 size_t gemm_w8_workspace_bytes(int M, int N, int splitk);
 void launch_gemm_w8(const GemmW8Args& a, hipStream_t s);
 
+// Skinny W8A16 GEMM (gemm_skinny_w8.hip): the arithmetic of launch_gemm_w8 for the 1 <= M <= 16 rows
+// of a decode step in the form of launch_gemm_skinny: the e4m3 bytes streamed straight to VGPRs in
+// 128-wide slices (one 128-byte line per weight row), converted in registers, a workgroup per
+// 16-column strip (SwiGLU: per 16-gate + 16-up block pair of the interleaved weight and scales), its
+// `waves` waves split K and sum in a fixed order. No atomics, no split-K across workgroups, no
+// workspace. Any N (SwiGLU: N % 32 == 0), K % 32 == 0, lda % 8 == 0, ldw % 16 == 0 (bytes), A and Wq
+// 16-byte aligned. No folded norm and no RoPE: fp8 plans run both as their own launches.
+struct GemmSkinnyW8Args {
+  const void* A;  // bf16 [M][lda]
+  int lda;
+  const void* Wq;  // e4m3 [N][ldw]
+  int ldw;
+  const float* scale;  // fp32 [N], positive
+  void* C;             // bf16 [M][ldc] (SwiGLU: N/2 columns)
+  int ldc;
+  const void* bias;  // bf16 [N] or nullptr
+  const void* R;     // bf16 [M][ldr] or nullptr
+  int ldr;
+  int M, N, K;
+  int act;  // DlsAct
+  float alpha;
+  int waves = 0;  // 4, 8, 16; 0: gemm_skinny_w8_waves
+};
+// false with *why (optional) naming the rule a launch breaks
+bool gemm_skinny_w8_takes(const GemmSkinnyW8Args& a, const char** why = nullptr);
+int gemm_skinny_w8_waves(int N, int K, int act);  // waves per workgroup the launcher picks: 4, 8 or 16
+bool launch_gemm_skinny_w8(const GemmSkinnyW8Args& a, hipStream_t s);  // false: nothing launched
+
 // Grouped W8A16 GEMM (gemm_w8_grouped.hip): the contract of launch_gemm_glds_grouped with the
 // arithmetic of launch_gemm_w8. n_groups groups in ONE launch; group g multiplies rows
 // [offsets[g], offsets[g+1]) — row r of A, or token row a_rows[r] of A — by its e4m3 weight

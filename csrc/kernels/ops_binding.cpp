@@ -1466,6 +1466,89 @@ at::Tensor gemm_skinny(const at::Tensor& a_in, const at::Tensor& w, const c10::o
   return c;
 }
 
+// Skinny W8A16 GEMM (gemm_skinny_w8.hip) for the M <= 16 rows of a decode step of an fp8-weight plan:
+// the three entries mirror gemm_skinny*. ldw is in bytes.
+GemmSkinnyW8Args skinny_w8_shape(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t act,
+                                 int64_t waves) {
+  GemmSkinnyW8Args g{};
+  g.lda = (int)lda;
+  g.ldw = (int)ldw;
+  g.M = (int)std::min<int64_t>(M, 1 << 30);
+  g.N = (int)std::min<int64_t>(N, 1 << 30);
+  g.K = (int)std::min<int64_t>(K, 1 << 30);
+  g.ldc = g.ldr = g.N;
+  g.act = (int)act;
+  static const float dummy = 1.f;
+  g.scale = &dummy;
+  g.waves = (int)waves;
+  return g;
+}
+std::string gemm_skinny_w8_refusal(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t act,
+                                   int64_t waves) {
+  const char* why = nullptr;
+  gemm_skinny_w8_takes(skinny_w8_shape(M, N, K, lda, ldw, act, waves), &why);
+  return why ? why : "";
+}
+int64_t gemm_skinny_w8_waves_py(int64_t N, int64_t K, int64_t act) {
+  return gemm_skinny_w8_waves((int)N, (int)K, (int)act);
+}
+
+at::Tensor gemm_skinny_w8(const at::Tensor& a_in, const at::Tensor& wq, const at::Tensor& scale,
+                          const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& residual,
+                          int64_t act, double alpha, const c10::optional<at::Tensor>& out, int64_t waves) {
+  check_bf16(a_in, "A");
+  at::Tensor a = as2d(a_in);
+  check_rows(a, "A");
+  TORCH_CHECK(wq.is_cuda() && wq.device() == a.device() && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "W must be a float8_e4m3fn tensor on A's GPU");
+  TORCH_CHECK(wq.dim() == 2, "W must be 2-D");
+  const int64_t M = a.size(0), K = a.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K, "W must be [N][K] with K = ", K, ", got ", wq.sizes());
+  TORCH_CHECK(wq.stride(1) == 1 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+              "W must have contiguous, 16-byte aligned rows");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == a.device() && scale.scalar_type() == at::kFloat &&
+                  scale.is_contiguous() && scale.numel() == N,
+              "scale must be a contiguous fp32 [N] tensor on A's GPU");
+  GemmSkinnyW8Args g = skinny_w8_shape(M, N, K, a.stride(0), wq.stride(0), act, waves);
+  const char* why = nullptr;
+  TORCH_CHECK(gemm_skinny_w8_takes(g, &why), "skinny fp8-weight GEMM: ", why ? why : "");
+  const int64_t NO = act == kActSwiglu ? N / 2 : N;
+  at::Tensor c;
+  if (out.has_value()) {
+    c = as2d(*out);
+    check_bf16(c, "out");
+    TORCH_CHECK(c.size(0) == M && c.size(1) == NO && c.stride(1) == 1 && c.device() == a.device(),
+                "out must be [M][N_out]");
+  } else {
+    c = at::empty({M, NO}, a.options());
+  }
+  g.A = a.data_ptr();
+  g.Wq = wq.data_ptr();
+  g.scale = scale.data_ptr<float>();
+  g.C = c.data_ptr();
+  g.ldc = (int)c.stride(0);
+  g.bias = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->device() == a.device(), "bias must be contiguous [N]");
+    g.bias = bias->data_ptr();
+  }
+  g.R = nullptr;
+  g.ldr = 0;
+  if (residual.has_value()) {
+    at::Tensor r = as2d(*residual);
+    check_bf16(r, "residual");
+    TORCH_CHECK(r.size(0) == M && r.size(1) == NO && r.stride(1) == 1 && r.device() == a.device(),
+                "residual must be [M][N_out]");
+    g.R = r.data_ptr();
+    g.ldr = (int)r.stride(0);
+  }
+  g.alpha = (float)alpha;
+  TORCH_CHECK(gemm_skinny_w8_takes(g, &why), "skinny fp8-weight GEMM: ", why ? why : "");
+  TORCH_CHECK(launch_gemm_skinny_w8(g, cur_stream()), "skinny fp8-weight GEMM refused the launch");
+  return c;
+}
+
 // gemm_grouped with fp8 expert weights (gemm_w8_grouped.hip): weights E x e4m3 [N][K], scales
 // E x fp32 [N]; w_ptrs / s_ptrs / out_ptrs: int64 [E] device tensors of their addresses (cached
 // by the caller: hipGraph-safe). config < 0: picked by (rows_hint, N, K).
@@ -1964,4 +2047,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ldw"), py::arg("act") = 0, py::arg("rope_S") = 1, py::arg("rope_D") = 4, py::arg("rope_cols") = 0,
         py::arg("ln_mode") = 0, py::arg("waves") = 0);
   m.def("gemm_skinny_waves", &gemm_skinny_waves_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
+  m.def("gemm_skinny_w8", &gemm_skinny_w8, py::arg("a"), py::arg("wq"), py::arg("scale"), py::arg("bias") = py::none(),
+        py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0, py::arg("out") = py::none(),
+        py::arg("waves") = 0);
+  m.def("gemm_skinny_w8_refusal", &gemm_skinny_w8_refusal, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"),
+        py::arg("ldw"), py::arg("act") = 0, py::arg("waves") = 0);
+  m.def("gemm_skinny_w8_waves", &gemm_skinny_w8_waves_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
 }

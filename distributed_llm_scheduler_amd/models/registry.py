@@ -155,6 +155,28 @@ def check_skinny_gemm(skinny_gemm: bool, kv_cache: "int | None", weight_dtype: s
                          "have no skinny form yet")
 
 
+def check_skinny_w8(skinny_w8: bool, kv_cache: "int | None", weight_dtype: str = "bf16", act_dtype: str = "bf16",
+                    skinny_gemm: bool = False) -> None:
+    """What ``skinny_w8=True`` (the e4m3-weight GEMMs of a decode step of at most
+    ops.SKINNY_W8_MAX_ROWS token rows on the weight-streaming kernel of ops.linear_skinny_w8)
+    needs of a plan. Both ``kv_dtype``s, ``generate`` and ``prefill_chunk`` (the token step takes
+    the kernel, the chunk step keeps the tiles) are accepted."""
+    if not skinny_w8:
+        return
+    if kv_cache is None:
+        raise ValueError("skinny_w8=True needs a KV cache (kv_cache=C): the skinny kernel is for the at most 16 "
+                         "token rows of a decode step")
+    if weight_dtype != "fp8":
+        raise ValueError(f"skinny_w8=True takes weight_dtype='fp8' only, got {weight_dtype!r}: it is the skinny form "
+                         "of the e4m3-weight GEMM (bf16 weights: skinny_gemm=True; mxfp4 has no skinny form yet)")
+    if act_dtype == "fp8":
+        raise ValueError("skinny_w8=True does not combine with act_dtype='fp8': W8A8 quantises the activations, and "
+                         "a skinny form of that GEMM is a follow-up")
+    if skinny_gemm:
+        raise ValueError("skinny_w8=True does not combine with skinny_gemm=True: skinny_gemm is the option of bf16 "
+                         "plans; an fp8 plan's bf16 GEMMs (a tied LM head) run skinny under skinny_w8 already")
+
+
 KV_DTYPES = ("bf16", "fp8")
 
 

@@ -748,6 +748,103 @@ def linear_skinny(x, w, bias=None, act=None, residual=None, alpha=1.0, out=None,
     return y
 
 
+# ------------------------------------------------- skinny fp8-weight GEMM (M <= 16, W8A16)
+
+# Token rows of a decode step of an fp8-weight plan with skinny_w8=True up to which the executor
+# sends e4m3 GEMM weights to the kernel of gemm_skinny_w8.hip, set as SKINNY_MAX_ROWS was: the
+# largest row count whose captured step won every alternating round against the plan without the
+# option (profiles/skinny_w8/step_bound_search.txt; README, "fp8-weight skinny GEMM"). llama3-8b-1l
+# won 5 of 5 rounds at 1, 2, 4, 8 and 16 rows (1.53x at one row, 1.21x at 8, 1.04x at 16), gpt2 at
+# every row count too (1.81x .. 1.58x): 16, the kernel's own limit. The tiles it replaces are built
+# for M = 512 and pay split-K slabs and a reduce launch at these shapes.
+SKINNY_W8_MAX_ROWS = 16
+
+
+def skinny_w8_waves(N: int, K: int, act=None) -> int:
+    """Waves per workgroup ``linear_skinny_w8`` launches with (the rule of gemm_skinny_w8_waves in
+    gemm_skinny_w8.hip, mirrored here for the CPU back end), read off the kernel table of
+    profiles/skinny_w8/: 4, and 8 for a plain strip at K >= 8192."""
+    a = ACT[act] if not isinstance(act, int) else act
+    if a == SWIGLU:
+        return 4
+    return 8 if (K + 127) // 128 >= 64 else 4
+
+
+def skinny_w8_refusal(M, N, K, act=None, waves=None, lda=None, ldw=None) -> Optional[str]:
+    """Why the skinny fp8-weight kernel does not take a launch (None: it does) — the rules of
+    gemm_skinny_w8_takes in gemm_skinny_w8.hip. ``ldw`` is in bytes."""
+    try:
+        a = ACT[act] if not isinstance(act, int) else act
+    except KeyError:
+        return f"unknown activation {act!r}"
+    lda, ldw = (K if lda is None else lda), (K if ldw is None else ldw)
+    if not 1 <= M <= SKINNY_ROWS_LIMIT:
+        return f"M = {M}: the kernel takes 1..{SKINNY_ROWS_LIMIT} rows"
+    if N < 1 or K < 32 or K % 32:
+        return f"N = {N}, K = {K}: N >= 1 and K a positive multiple of 32"
+    if lda % 8 or lda < K:
+        return "the row stride of x must be a multiple of 8 elements"
+    if ldw % 16 or ldw < K:
+        return "the row stride of q must be a multiple of 16 bytes"
+    if a not in (0, 1, 2, 3, SWIGLU):
+        return f"unknown activation {act!r}"
+    if a == SWIGLU and N % 32:
+        return f"SwiGLU needs N % 32 == 0, N = {N}"
+    if waves is not None and waves not in SKINNY_WAVES:
+        return f"waves = {waves}: one of {SKINNY_WAVES}"
+    return None
+
+
+def skinny_w8_ok(M, N, K, act=None, waves=None, lda=None, ldw=None) -> bool:
+    """Does the skinny fp8-weight kernel take an [M][K] x [N][K]^T launch with this epilogue?"""
+    return skinny_w8_refusal(M, N, K, act, waves, lda, ldw) is None
+
+
+def linear_skinny_w8(x, q, scale, bias=None, act=None, residual=None, alpha=1.0, out=None, waves=None):
+    """:func:`linear_w8` — ``act(alpha * scale[n] * sum_k x[m][k] * q[n][k] + bias[n]) + residual``,
+    ``q`` e4m3 [N, K], ``scale`` fp32 [N] (any positive values) — for the 1 <= M <= 16 rows of a
+    decode step on the weight-streaming kernel of gemm_skinny_w8.hip (GPU): the fp8 bytes go
+    straight to registers in 128-wide slices and are converted there, a workgroup per 16-column
+    strip, ``waves`` waves (4, 8, 16; None: :func:`skinny_w8_waves`) split K inside it and sum in
+    a fixed order — no atomics, no workspace, two launches bit-identical, and a row's result does
+    not depend on the other rows of the launch. ``act="swiglu"`` takes the gate/up interleaved
+    rows and scales. What the kernel does not take raises ``ValueError``: M > 16, K % 32 != 0,
+    SwiGLU with N % 32 != 0, a ``q`` that is not float8_e4m3fn, a ``scale`` that is not fp32 [N],
+    other operands that are not bf16, rows that are not 16-byte aligned. CPU tensors run
+    :func:`ref_linear` on the dequantised weight, as :func:`linear_w8` does."""
+    if x.dim() < 2 or q.dim() != 2 or q.shape[1] != x.shape[-1]:
+        raise ValueError("linear_skinny_w8: x [..., K] and q [N][K]")
+    if q.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"linear_skinny_w8: the weight must be float8_e4m3fn, got {q.dtype}")
+    a = ACT.get(act, -1) if not isinstance(act, int) else act
+    K, N = x.shape[-1], q.shape[0]
+    M = x.numel() // K
+    x2 = x.reshape(M, K)
+    if x.dtype != torch.bfloat16:
+        raise ValueError("linear_skinny_w8: x must be bf16")
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != N or not scale.is_contiguous():
+        raise ValueError(f"linear_skinny_w8: scale must be a contiguous fp32 [{N}] tensor")
+    if x2.stride(1) != 1 or q.stride(1) != 1 or x2.data_ptr() % 16 or q.data_ptr() % 16:
+        raise ValueError("linear_skinny_w8: rows of x and q must be contiguous and 16-byte aligned")
+    why = skinny_w8_refusal(M, N, K, a if a >= 0 else act, waves, x2.stride(0) if M > 1 else K, q.stride(0))
+    if why is not None:
+        raise ValueError(f"linear_skinny_w8: {why}")
+    n_out = N // 2 if a == SWIGLU else N
+    for name, t, shp in (("bias", bias, (N,)), ("residual", residual, (M, n_out)), ("out", out, (M, n_out))):
+        if t is not None and (t.dtype != torch.bfloat16 or t.numel() != math.prod(shp)):
+            raise ValueError(f"linear_skinny_w8: {name} must be bf16 {list(shp)}")
+    r2 = residual if residual is None or residual.dim() == 2 else residual.reshape(M, n_out)
+    o2 = out if out is None or out.dim() == 2 else out.view(M, n_out)
+    if _gpu(x):
+        y = ext().gemm_skinny_w8(x2, q, scale, bias, r2, a, float(alpha), o2, int(waves or 0))
+        return y.view(x.shape[:-1] + (n_out,)) if out is None else out
+    y = ref_linear(x2, dequantize_fp8(q, scale, torch.float32), bias, a, r2, alpha).reshape(x.shape[:-1] + (n_out,))
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
 def mlp_fused_ok(M, H, F, Hout) -> bool:
     """Does the one-launch MLP block (gemm_fused.hip) take this shape on this GPU?"""
     return bool(ext().mlp_fused_ok(int(M), int(H), int(F), int(Hout)))

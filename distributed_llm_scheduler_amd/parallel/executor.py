@@ -196,21 +196,28 @@ class DAGExecutor:
                  trace: bool = False, debug: bool = False, model_name: Optional[str] = None,
                  input_parts: Optional[Dict[str, List[str]]] = None,
                  requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16",
-                 prefill_chunk: Optional[int] = None, skinny_gemm: bool = False):
+                 prefill_chunk: Optional[int] = None, skinny_gemm: bool = False, skinny_w8: bool = False):
         self.tasks = {t.id: t for t in tasks}
         # runtime.plan skinny_gemm=True: the dense bf16 GEMMs of a step of at most ops.SKINNY_MAX_ROWS
         # token rows go to ops.linear_skinny (_skinny_pick). DLS_SKINNY=0 turns the dispatch off (the
         # launches of the plan without the option), DLS_SKINNY=all takes every step of up to 16 rows
         # and the LM head whatever the two measured constants say.
+        # runtime.plan skinny_w8=True (an fp8-weight plan): the e4m3 GEMM weights of a token step of at
+        # most ops.SKINNY_W8_MAX_ROWS rows go to ops.linear_skinny_w8 (_skinny_w8_pick), the plan's bf16
+        # GEMM weights (a tied LM head) through _skinny_pick under the same row limit; DLS_SKINNY as above.
         self.skinny_gemm = bool(skinny_gemm)
+        self.skinny_w8 = bool(skinny_w8)
         self._skinny_mode = os.environ.get("DLS_SKINNY", "1")
-        self._skinny_on = self.skinny_gemm and torch.device(device).type == "cuda" and self._skinny_mode != "0"
+        self._skinny_on = ((self.skinny_gemm or self.skinny_w8) and torch.device(device).type == "cuda"
+                           and self._skinny_mode != "0")
+        self._skinny_limit = (ops.SKINNY_ROWS_LIMIT if self._skinny_mode == "all" else
+                              ops.SKINNY_W8_MAX_ROWS if self.skinny_w8 else ops.SKINNY_MAX_ROWS)
         self._skinny: Dict[Tuple[str, str], str] = {}  # (task, weight) -> "skinny" or why the tiles ran
         # rows of the token step: above the dispatch's limit no GEMM of it runs skinny, and the step
         # keeps the launches of the plan without the option, statistics hand-off included
         rows = max([math.prod(t.op.out_shape[:-1]) for t in tasks
                     if t.op is not None and t.op.kind in ("linear", "lm_head", "attention", "swiglu_mlp")] or [0])
-        self._skinny_rows = rows <= (ops.SKINNY_ROWS_LIMIT if self._skinny_mode == "all" else ops.SKINNY_MAX_ROWS)
+        self._skinny_rows = rows <= self._skinny_limit
         self._cur_task: Optional[str] = None           # head task of the kernel group in flight
         # runtime.plan prefill_chunk=Tc: the program also runs as a chunk step of Tc tokens per sequence
         self.prefill_chunk = int(prefill_chunk) if prefill_chunk else None
@@ -1412,7 +1419,7 @@ class DAGExecutor:
         W = self._w(w_name)
         M, K, N = x.numel() // x.shape[-1], x.shape[-1], W.shape[0]
         every = self._skinny_mode == "all"
-        limit = ops.SKINNY_ROWS_LIMIT if every else ops.SKINNY_MAX_ROWS
+        limit = self._skinny_limit
         why = None
         if W.dtype != torch.bfloat16:
             why = f"{str(W.dtype).replace('torch.', '')} weight"
@@ -1424,6 +1431,23 @@ class DAGExecutor:
             why = "vocabulary-sized projection (ops.SKINNY_LMHEAD)"
         else:
             why = ops.skinny_refusal(M, N, K, act, rope, lda=x.stride(0) if M > 1 else K, ldw=W.stride(0))
+        self._skinny[(self._cur_task, w_name)] = why or "skinny"
+        return why is None
+
+    def _skinny_w8_pick(self, x, w_name, W, act=None) -> bool:
+        """Does the GEMM of the group in flight on the e4m3 weight ``W`` go to ops.linear_skinny_w8?
+        A plan with skinny_w8 on a GPU, bf16 activations, a token step of at most
+        ops.SKINNY_W8_MAX_ROWS rows (a chunk step keeps the tiles) and a shape the kernel takes. The
+        answer or the reason of the fallback is kept in ``_skinny[(task, weight)]``."""
+        if not (self.skinny_w8 and self._skinny_on) or self._chunk_on:
+            return False
+        M, K, N = x.numel() // x.shape[-1], x.shape[-1], W.shape[0]
+        if self._a8:
+            why = "fp8 activations"
+        elif M > self._skinny_limit:
+            why = f"M = {M} rows, above {self._skinny_limit}"
+        else:
+            why = ops.skinny_w8_refusal(M, N, K, act, lda=x.stride(0) if M > 1 else K, ldw=W.stride(0))
         self._skinny[(self._cur_task, w_name)] = why or "skinny"
         return why is None
 
@@ -1454,6 +1478,8 @@ class DAGExecutor:
         scale = self._w(w_name + SCALE_SUFFIX)
         if interleave:
             bias = self._prep_w8(w_name, W, scale, bias)
+        if not mx and self._skinny_w8_pick(x, w_name, W, act):  # no split-K workspace: one launch, no reduce
+            return ops.linear_skinny_w8(x, W, scale, bias, act=act, residual=residual, out=out)
         ws = None
         M = x.numel() // x.shape[-1]
         if self._a8 and xq is None:

@@ -78,7 +78,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
          generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False,
-         skinny_gemm: bool = False) -> Plan:
+         skinny_gemm: bool = False, skinny_w8: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -199,6 +199,16 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     Refused with ``ValueError``: no ``kv_cache``, a ``weight_dtype`` other than ``"bf16"``. The key
     enters ``Plan.args`` only when set.
 
+    ``skinny_w8=True`` (with ``kv_cache`` and ``weight_dtype="fp8"``; either ``kv_dtype``, with or
+    without ``generate`` and ``prefill_chunk``): the executor sends the e4m3-weight GEMMs of a token
+    step of at most ``ops.SKINNY_W8_MAX_ROWS`` rows to the weight-streaming kernel of
+    ``ops.linear_skinny_w8`` instead of the tiles of ``ops.linear_w8``, and the plan's bf16 GEMMs
+    (a tied LM head) to ``ops.linear_skinny``; norms, RoPE and attention launches are untouched, a
+    chunk step keeps the tiles. The DAG, the placement, the programs and the costs are those of the
+    plan without the option. Refused with ``ValueError``: no ``kv_cache``, a ``weight_dtype`` other
+    than ``"fp8"``, ``act_dtype="fp8"``, and ``skinny_gemm=True`` together with it. The key enters
+    ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -239,6 +249,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_moe_decode(moe_decode, registry.get_config(model), kv_cache, weight_dtype, prefill_chunk)
     if moe_decode:  # (only when set, as generate)
         args["moe_decode"] = True
+    registry.check_skinny_w8(skinny_w8, kv_cache, weight_dtype, act_dtype, skinny_gemm)
+    if skinny_w8:  # (only when set, as skinny_gemm)
+        args["skinny_w8"] = True
     registry.check_skinny_gemm(skinny_gemm, kv_cache, weight_dtype)
     if skinny_gemm:  # (only when set, as generate: the executor's choice of kernel, nothing the DAG sees)
         args["skinny_gemm"] = True
@@ -465,6 +478,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["moe_decode"] = (saved.get("moe_decode", False), args.get("moe_decode", False))
     if saved.get("skinny_gemm", False) != args.get("skinny_gemm", False):
         mismatch["skinny_gemm"] = (saved.get("skinny_gemm", False), args.get("skinny_gemm", False))
+    if saved.get("skinny_w8", False) != args.get("skinny_w8", False):
+        mismatch["skinny_w8"] = (saved.get("skinny_w8", False), args.get("skinny_w8", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -803,4 +818,5 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
     return DAGExecutor(p.tasks, p.programs[rank], store or make_store(p), device, model_cfg=p.cfg,
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
                        input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"),
-                       prefill_chunk=p.args.get("prefill_chunk"), skinny_gemm=p.args.get("skinny_gemm", False))
+                       prefill_chunk=p.args.get("prefill_chunk"), skinny_gemm=p.args.get("skinny_gemm", False),
+                       skinny_w8=p.args.get("skinny_w8", False))
