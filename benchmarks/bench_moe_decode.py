@@ -15,6 +15,13 @@ reaches on K/V bytes. Exit status 2 if the skinny kernel is not the faster in ev
 where the executor takes it (M <= ops.MOE_SKINNY_MAX_ROWS).
 
     python benchmarks/bench_moe_decode.py [--rounds 3] [--sets 8] [--out DIR] [--step [--max-rows N]] [--skip-kernels]
+                                          [--weight-dtype fp8-experts]
+
+--weight-dtype fp8-experts: the same two measurements for ops.gemm_grouped_skinny_w8
+(csrc/kernels/gemm_grouped_skinny_w8.hip) under the same protocol. The kernel table holds every
+(W, strip, nt) instance next to ``ops.gemm_grouped_w8`` on the same inputs (the launches of a plan
+without moe_skinny_w8) and the bf16 ``ops.gemm_grouped_skinny``; TB/s are of routed fp8 bytes. --step runs the
+plan with moe_skinny_w8=True and --max-rows sets ops.MOE_SKINNY_W8_MAX_ROWS.
 
 --step: the decode step of mixtral-8x7b-1l (runtime.plan moe_decode=True, T 1; B 1 from a context
 of 512 and of 8000 positions, B 2, 4, 8, 16 from 8000) as one captured hipGraph with the skinny
@@ -137,19 +144,84 @@ def kernels(a):
     return lines + tail, ok
 
 
-def step_ab(model="mixtral-8x7b-1l", C=8192, cases=((1, 1, 512), (1, 1, 8000), (2, 1, 8000), (4, 1, 8000), (8, 1, 8000), (16, 1, 8000)), steps=10, rounds=5):
+def kernels_w8(a):
+    """Every instance of the fp8 skinny grouped kernel against gemm_grouped_w8 and the bf16 skinny kernel."""
+    mk = lambda ts: torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=DEV)  # noqa: E731
+    w13 = [torch.empty(2 * F, H, dtype=torch.bfloat16, device=DEV).normal_(0, 0.02) for _ in range(E)]
+    w2 = [torch.empty(H, F, dtype=torch.bfloat16, device=DEV).normal_(0, 0.02) for _ in range(E)]
+    q13, s13 = zip(*(ops.quantize_fp8(w) for w in w13))
+    q2, s2 = zip(*(ops.quantize_fp8(w) for w in w2))
+    d13, d2 = [ops.dequantize_fp8(q, s) for q, s in zip(q13, s13)], [ops.dequantize_fp8(q, s) for q, s in zip(q2, s2)]
+    pw13, pw2, pq13, ps13, pq2, ps2 = mk(w13), mk(w2), mk(q13), mk(s13), mk(q2), mk(s2)
+    inst = lambda strips: [(W, st, nt) for W in (4, 8) for st in strips for nt in (0, 1)]  # noqa: E731
+    lines = [f"{'launch':8s} {'M':>3s} {'candidate':>22s} {'us':>8s} {'min':>8s} {'max':>8s} {'routed MB':>10s} {'TB/s':>6s}"]
+    print(lines[0], flush=True)
+    for M in (1, 4, 8, 16):
+        R = M * TOPK
+        g = torch.Generator(device=DEV).manual_seed(M)
+        x = torch.randn(M, H, device=DEV, generator=g).bfloat16()
+        hb = (0.5 * torch.randn(R, F, device=DEV, generator=g)).bfloat16()
+        hout = torch.empty(R, F, dtype=torch.bfloat16, device=DEV)
+        outs = [torch.empty(M, H, dtype=torch.bfloat16, device=DEV) for _ in range(E)]
+        optr = mk(outs)
+        rts = routings(M, a.sets, 100 + M)
+        hint = max(1, R // E)
+
+        def gu(fn, *w, **kw):
+            return lambda i: fn(x, *w, rts[i % a.sets][1], act="swiglu", out=hout, a_rows=rts[i % a.sets][0], **kw)
+
+        def dn(fn, *w, **kw):
+            return lambda i: fn(hb, *w, rts[i % a.sets][1], outs=outs, out_ptrs=optr, **kw)
+
+        new = ops.gemm_grouped_skinny_w8
+        cands = {"gate/up": [(f"skinny-w8 W{W} s{st} {'nt' if nt else 'plain'}",
+                              gu(new, q13, s13, w_ptrs=pq13, s_ptrs=ps13, waves=W, strip=st, nt=nt)) for W, st, nt in inst((16,))]
+                 + [("grouped_w8", gu(ops.gemm_grouped_w8, q13, s13, w_ptrs=pq13, s_ptrs=ps13, rows_hint=hint)),
+                    ("bf16 skinny", gu(ops.gemm_grouped_skinny, w13, w_ptrs=pw13))],
+                 "down": [(f"skinny-w8 W{W} s{st} {'nt' if nt else 'plain'}",
+                           dn(new, q2, s2, w_ptrs=pq2, s_ptrs=ps2, waves=W, strip=st, nt=nt)) for W, st, nt in inst((16, 32))]
+                 + [("grouped_w8", dn(ops.gemm_grouped_w8, q2, s2, w_ptrs=pq2, s_ptrs=ps2, rows_hint=hint)),
+                    ("bf16 skinny", dn(ops.gemm_grouped_skinny, w2, w_ptrs=pw2))]}
+        reps = max(4, a.sets)
+        for what, cs in cands.items():
+            for name, f in cs:  # every candidate's output against an fp32 product of the routed rows first
+                f(0)
+                ws = (w13 if what == "gate/up" else w2) if name.startswith("bf16") else (d13 if what == "gate/up" else d2)
+                check(x if what == "gate/up" else hb, ws, rts[0], hout if what == "gate/up" else outs, what == "gate/up",
+                      what == "down")
+            t = {name: [] for name, _ in cs}
+            for _ in range(a.rounds):  # same device, the candidates alternating
+                for name, f in cs:
+                    t[name].append(tuning._graph_time(f, reps=reps))
+            fp8 = statistics.mean(rts[i % a.sets][2] for i in range(reps)) * (2 * F * H if what == "gate/up" else H * F)
+            for name, _ in cs:
+                med = statistics.median(t[name])
+                lines.append(f"{what:8s} {M:3d} {name:>22s} {med:8.1f} {min(t[name]):8.1f} {max(t[name]):8.1f} "
+                             f"{fp8 / 1e6:10.1f} {fp8 / med / 1e6:6.2f}")
+                print(lines[-1], flush=True)
+    lines.append(f"us: median device time per call of a hipGraph of calls cycling through {a.sets} routings, {a.rounds} rounds, "
+                 "the candidates alternating; routed MB / TB/s: e4m3 weight bytes of the experts with rows (the bf16 "
+                 "kernel reads twice as many)")
+    return lines
+
+
+def step_ab(model="mixtral-8x7b-1l", C=8192, cases=((1, 1, 512), (1, 1, 8000), (2, 1, 8000), (4, 1, 8000), (8, 1, 8000), (16, 1, 8000)), steps=10, rounds=5,
+            weight_dtype="bf16"):
     from distributed_llm_scheduler_amd.parallel import executor as exm
     from distributed_llm_scheduler_amd.parallel import runtime
 
     dev = torch.device("cuda:0")
     lines = []
+    w8 = weight_dtype == "fp8-experts"
+    bound = "MOE_SKINNY_W8_MAX_ROWS" if w8 else "MOE_SKINNY_MAX_ROWS"
     for B, T, past in cases:
-        if B * T > ops.MOE_SKINNY_MAX_ROWS:
-            lines.append(f"{model}  B {B}  T {T}: more than ops.MOE_SKINNY_MAX_ROWS = {ops.MOE_SKINNY_MAX_ROWS} token rows, "
+        if B * T > getattr(ops, bound):
+            lines.append(f"{model}  B {B}  T {T}: more than ops.{bound} = {getattr(ops, bound)} token rows, "
                          "the grouped kernels either way")
             print(lines[-1], flush=True)
             continue
-        p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, moe_decode=True)
+        p = runtime.plan(model, world=1, seq=T, batch=B, kv_cache=C, moe_decode=True,
+                         **(dict(weight_dtype=weight_dtype, moe_skinny_w8=True) if w8 else {}))
         store = runtime.make_store(p, device_init=runtime.device_init_ok(p, 0))
         exs = {}
         for what, flag in (("off", False), ("on", True)):
@@ -180,7 +252,7 @@ def step_ab(model="mixtral-8x7b-1l", C=8192, cases=((1, 1, 512), (1, 1, 8000), (
             for what in ("off", "on"):
                 t[what].append(timed(exs[what]))
         med = {k: statistics.median(v) for k, v in t.items()}
-        lines.append(f"{model}  B {B}  T {T}  past {past}  cache {C}: {med['off']:.1f} us per step with DLS_MOE_SKINNY=0 "
+        lines.append(f"{model} {weight_dtype}  B {B}  T {T}  past {past}  cache {C}: {med['off']:.1f} us per step with DLS_MOE_SKINNY=0 "
                      f"(min {min(t['off']):.1f}, max {max(t['off']):.1f}), {med['on']:.1f} us with the skinny "
                      f"{' + '.join(next(iter(exs['on']._moe_skinny.values())))} "
                      f"(min {min(t['on']):.1f}, max {max(t['on']):.1f}): {med['off'] / med['on']:.2f}x, faster in "
@@ -199,6 +271,8 @@ def main():
     ap.add_argument("--out", default=None, help="directory for kernels.txt / step.txt")
     ap.add_argument("--step", action="store_true", help="also the mixtral-8x7b-1l decode step, skinny launches off and on")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8-experts"],
+                    help="fp8-experts: ops.gemm_grouped_skinny_w8 and the plan option moe_skinny_w8")
     ap.add_argument("--max-rows", type=int, default=None,
                     help="with --step: run it with ops.MOE_SKINNY_MAX_ROWS set to this (a bound search: the default "
                          "measures what the executor does)")
@@ -208,7 +282,14 @@ def main():
     ok = True
     if a.out:
         os.makedirs(a.out, exist_ok=True)
-    if not a.skip_kernels:
+    w8 = a.weight_dtype == "fp8-experts"
+    if not a.skip_kernels and w8:
+        lines = kernels_w8(a)
+        if a.out:
+            with open(os.path.join(a.out, "kernels.txt"), "w") as f:
+                f.write("fp8 skinny grouped expert GEMM, every instance, Mixtral-8x7B shapes\n" + "\n".join(lines) + "\n")
+        torch.cuda.empty_cache()
+    elif not a.skip_kernels:
         lines, ok = kernels(a)
         if a.out:
             with open(os.path.join(a.out, "kernels.txt"), "w") as f:
@@ -217,8 +298,8 @@ def main():
         torch.cuda.empty_cache()
     if a.step:
         if a.max_rows is not None:
-            ops.MOE_SKINNY_MAX_ROWS = a.max_rows  # (read by the executor at every step)
-        lines = step_ab()
+            setattr(ops, "MOE_SKINNY_W8_MAX_ROWS" if w8 else "MOE_SKINNY_MAX_ROWS", a.max_rows)  # (read at every step)
+        lines = step_ab(weight_dtype=a.weight_dtype)
         if a.out:
             with open(os.path.join(a.out, "step.txt"), "w") as f:
                 f.write("\n".join(lines) + "\n")

@@ -251,6 +251,38 @@ bool gemm_skinny_w8_takes(const GemmSkinnyW8Args& a, const char** why = nullptr)
 int gemm_skinny_w8_waves(int N, int K, int act);  // waves per workgroup the launcher picks: 4, 8 or 16
 bool launch_gemm_skinny_w8(const GemmSkinnyW8Args& a, hipStream_t s);  // false: nothing launched
 
+// Grouped skinny W8A16 GEMM (gemm_grouped_skinny_w8.hip): the contract of launch_gemm_grouped_skinny
+// with e4m3 weights (w_ptrs[g]: [N][K] bytes, K contiguous) and one fp32 scale per output channel
+// (s_ptrs[g]: [N], positive), applied once after the fp32 accumulation, before SwiGLU; for SwiGLU
+// the rows of q AND scale are gate/up-interleaved in blocks of 16. 128-wide K slices streamed
+// straight to VGPRs and converted there, a workgroup per (group, strip), `waves` waves split K and
+// sum in a fixed order. K % 32 == 0, N % 16 == 0 (SwiGLU: N % 32 == 0, N/2 outputs). The grid
+// depends on (n_groups, N, strip) only. No atomics, no workspace, no host sync.
+struct GemmGroupedSkinnyW8Args {
+  const void* A;  // bf16 [a_total][lda], lda % 8 == 0, 16-byte aligned
+  int lda;
+  int a_total;         // rows of A (a_rows values are clamped into it)
+  const int* a_rows;   // device int32 [R] or nullptr
+  const int* offsets;  // device int32 [n_groups + 1]
+  const unsigned long long* w_ptrs;  // device [n_groups]: e4m3 [N][K], 16-byte aligned
+  const unsigned long long* s_ptrs;  // device [n_groups]: fp32 [N]
+  const unsigned long long* c_ptrs;  // device [n_groups] or nullptr
+  void* C;                           // bf16 [R][ldc] when c_ptrs == nullptr
+  int ldc;
+  int compact_rows;
+  int R, N, K;  // R: rows all groups cover together (offsets are clamped to it)
+  int act;
+  int n_groups;
+  int waves = 0;  // 4, 8; 0: gemm_grouped_skinny_w8_waves
+  int strip = 0;  // plain columns per workgroup, 16 or 32 (SwiGLU: 16 outputs); 0: gemm_grouped_skinny_w8_strip
+  int nt = -1;    // weight loads: 1 streaming (nt), 0 default cache policy; -1: gemm_grouped_skinny_w8_nt
+};
+bool gemm_grouped_skinny_w8_takes(int N, int K, int act);
+int gemm_grouped_skinny_w8_waves(int N, int K, int act);
+int gemm_grouped_skinny_w8_strip(int N, int K, int act);
+bool gemm_grouped_skinny_w8_nt(int N, int K, int act);
+bool launch_gemm_grouped_skinny_w8(const GemmGroupedSkinnyW8Args& a, hipStream_t s);  // false: nothing launched
+
 // Grouped W8A16 GEMM (gemm_w8_grouped.hip): the contract of launch_gemm_glds_grouped with the
 // arithmetic of launch_gemm_w8. n_groups groups in ONE launch; group g multiplies rows
 // [offsets[g], offsets[g+1]) — row r of A, or token row a_rows[r] of A — by its e4m3 weight

@@ -1634,6 +1634,102 @@ void gemm_grouped_w8(const at::Tensor& x, const std::vector<at::Tensor>& weights
   launch_gemm_w8_grouped(g, cur_stream());
 }
 
+// gemm_grouped_w8 on the skinny kernel (gemm_grouped_skinny_w8.hip): the same tensors and checks;
+// what the kernel does not take (act none / SwiGLU, K % 32 == 0, N % 16 == 0 — SwiGLU N % 32 == 0 —,
+// 16-byte aligned rows, waves 4 / 8, strip 16 / 32) is refused here. waves / strip 0 and nt < 0: the
+// launcher's rule.
+void gemm_grouped_skinny_w8(const at::Tensor& x, const std::vector<at::Tensor>& weights,
+                            const std::vector<at::Tensor>& scales, const at::Tensor& w_ptrs, const at::Tensor& s_ptrs,
+                            const at::Tensor& offsets, int64_t act, const c10::optional<at::Tensor>& out,
+                            const std::vector<at::Tensor>& outs, const c10::optional<at::Tensor>& out_ptrs,
+                            const c10::optional<at::Tensor>& a_rows, int64_t waves, int64_t strip, int64_t nt) {
+  const int64_t E = (int64_t)weights.size();
+  check_bf16(x, "x");
+  check_rows(x, "x");
+  TORCH_CHECK(E > 0 && (int64_t)scales.size() == E, "one scale tensor per expert weight");
+  const int* arp = nullptr;
+  if (a_rows.has_value()) {
+    TORCH_CHECK(a_rows->is_cuda() && a_rows->scalar_type() == at::kInt && a_rows->is_contiguous(),
+                "a_rows: contiguous int32 on the GPU");
+    arp = a_rows->data_ptr<int32_t>();
+  }
+  const int64_t R = a_rows.has_value() ? a_rows->numel() : x.size(0), K = x.size(1), N = weights[0].size(0);
+  const bool sw = act == kActSwiglu;
+  const int64_t NO = sw ? N / 2 : N;
+  TORCH_CHECK(gemm_grouped_skinny_w8_takes((int)N, (int)K, (int)act),
+              "skinny grouped fp8-weight GEMM: act none or SwiGLU, K % 32 == 0, N % 16 == 0 (SwiGLU: N % 32 == 0)");
+  TORCH_CHECK(waves == 0 || waves == 4 || waves == 8, "skinny grouped fp8-weight GEMM: waves in {4, 8}");
+  TORCH_CHECK(strip == 0 || strip == 16 || (strip == 32 && !sw),
+              "skinny grouped fp8-weight GEMM: strip 16, or 32 without SwiGLU");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "skinny grouped fp8-weight GEMM: rows of x must be 16-byte aligned");
+  for (int64_t e = 0; e < E; ++e) {
+    const auto& w = weights[e];
+    const auto& sc = scales[e];
+    TORCH_CHECK(w.is_cuda() && w.device() == x.device() && w.scalar_type() == at::kFloat8_e4m3fn,
+                "expert weights must be float8_e4m3fn tensors on x's GPU");
+    TORCH_CHECK(w.is_contiguous() && w.dim() == 2 && w.size(0) == N && w.size(1) == K &&
+                    reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                "expert weights: contiguous, 16-byte aligned [N][K]");
+    TORCH_CHECK(sc.is_cuda() && sc.device() == x.device() && sc.scalar_type() == at::kFloat && sc.is_contiguous() &&
+                    sc.numel() == N,
+                "expert scales: contiguous fp32 [N] on x's GPU");
+  }
+  TORCH_CHECK(w_ptrs.is_cuda() && w_ptrs.scalar_type() == at::kLong && w_ptrs.numel() == E, "w_ptrs int64 [E]");
+  TORCH_CHECK(s_ptrs.is_cuda() && s_ptrs.scalar_type() == at::kLong && s_ptrs.numel() == E, "s_ptrs int64 [E]");
+  TORCH_CHECK(offsets.is_cuda() && offsets.scalar_type() == at::kInt && offsets.numel() == E + 1,
+              "offsets int32 [E+1]");
+  GemmGroupedSkinnyW8Args g{};
+  g.A = x.data_ptr();
+  g.lda = (int)x.stride(0);
+  g.a_total = (int)x.size(0);
+  g.a_rows = arp;
+  g.offsets = offsets.data_ptr<int32_t>();
+  g.w_ptrs = reinterpret_cast<const unsigned long long*>(w_ptrs.data_ptr<int64_t>());
+  g.s_ptrs = reinterpret_cast<const unsigned long long*>(s_ptrs.data_ptr<int64_t>());
+  g.R = (int)R;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.act = (int)act;
+  g.n_groups = (int)E;
+  g.waves = (int)waves;
+  g.strip = (int)strip;
+  g.nt = (int)nt;
+  if (out_ptrs.has_value()) {
+    TORCH_CHECK((int64_t)outs.size() == E && out_ptrs->is_cuda() && out_ptrs->scalar_type() == at::kLong &&
+                    out_ptrs->numel() == E,
+                "compact outputs: E tensors + int64 [E] addresses");
+    const int64_t cap = outs[0].size(0);
+    for (const auto& o : outs) {
+      check_bf16(o, "expert output");
+      TORCH_CHECK(o.dim() == 2 && o.is_contiguous() && o.size(1) == NO && o.size(0) == cap,
+                  "expert outputs: E contiguous [cap][N'] tensors");
+    }
+    g.ldc = (int)NO;
+    g.compact_rows = (int)cap;
+    g.c_ptrs = reinterpret_cast<const unsigned long long*>(out_ptrs->data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(out.has_value(), "grouped GEMM needs `out` or compact outputs");
+    check_bf16(*out, "out");
+    check_rows(*out, "out");
+    TORCH_CHECK(out->size(0) == R && out->size(1) == NO, "out must be [R][N'] (N' = N/2 with SwiGLU)");
+    g.C = out->data_ptr();
+    g.ldc = (int)out->stride(0);
+  }
+  if (R == 0 || x.size(0) == 0) return;
+  TORCH_CHECK(launch_gemm_grouped_skinny_w8(g, cur_stream()), "skinny grouped fp8-weight GEMM: launch refused");
+}
+
+int64_t gemm_grouped_skinny_w8_waves_py(int64_t N, int64_t K, int64_t act) {
+  return gemm_grouped_skinny_w8_waves((int)N, (int)K, (int)act);
+}
+int64_t gemm_grouped_skinny_w8_strip_py(int64_t N, int64_t K, int64_t act) {
+  return gemm_grouped_skinny_w8_strip((int)N, (int)K, (int)act);
+}
+bool gemm_grouped_skinny_w8_nt_py(int64_t N, int64_t K, int64_t act) {
+  return gemm_grouped_skinny_w8_nt((int)N, (int)K, (int)act);
+}
+
 // gemm_grouped with MXFP4 expert weights and fp8 activation rows (gemm_w4a8_grouped.hip): xq e4m3
 // [rows][K] with one fp32 scale per row (indexed through a_rows when given); weights E x uint8
 // [N][K/2], block scales E x uint8 [N][K/32]; pointer arrays, outputs and config as gemm_grouped_w8.
@@ -2038,6 +2134,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_grouped_skinny", &gemm_grouped_skinny, py::arg("x"), py::arg("weights"), py::arg("w_ptrs"),
         py::arg("offsets"), py::arg("act") = 0, py::arg("out") = py::none(),
         py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(), py::arg("a_rows") = py::none());
+  m.def("gemm_grouped_skinny_w8", &gemm_grouped_skinny_w8, py::arg("x"), py::arg("weights"), py::arg("scales"),
+        py::arg("w_ptrs"), py::arg("s_ptrs"), py::arg("offsets"), py::arg("act") = 0, py::arg("out") = py::none(),
+        py::arg("outs") = std::vector<at::Tensor>{}, py::arg("out_ptrs") = py::none(), py::arg("a_rows") = py::none(),
+        py::arg("waves") = 0, py::arg("strip") = 0, py::arg("nt") = -1);
+  m.def("gemm_grouped_skinny_w8_waves", &gemm_grouped_skinny_w8_waves_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
+  m.def("gemm_grouped_skinny_w8_strip", &gemm_grouped_skinny_w8_strip_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
+  m.def("gemm_grouped_skinny_w8_nt", &gemm_grouped_skinny_w8_nt_py, py::arg("N"), py::arg("K"), py::arg("act") = 0);
   m.def("gemm_skinny", &gemm_skinny, py::arg("a"), py::arg("w"), py::arg("bias") = py::none(),
         py::arg("residual") = py::none(), py::arg("act") = 0, py::arg("alpha") = 1.0, py::arg("out") = py::none(),
         py::arg("ln_colsum") = py::none(), py::arg("ln_mode") = 0, py::arg("ln_eps") = 1e-5,

@@ -178,7 +178,8 @@ def _build_ops(kern, hdrs, hosts, host_hdrs, force, verbose, jobs) -> str:
                 "attn_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_decode_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 # its only fp32 VALU math is the one-wave epilogue: scalar fp32 ops, no packed forms
-                "gemm_skinny_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "gemm_skinny_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                "gemm_grouped_skinny_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
     def compile_kernel(src):
         # objects are stamped by content too (an mtime check misses an edit made while an

@@ -35,7 +35,9 @@ the number of new tokens per step and every attention node keeps a KV cache of C
 --moe-decode (with --kv-cache and an MoE model: decode steps of a Mixtral plan, the expert GEMMs of a step of a
 few token rows on the skinny grouped kernel), --skinny-gemm (with --kv-cache and bf16 weights: the dense GEMMs of
 a step of a few token rows on the weight-streaming skinny kernel), --skinny-w8 (with --kv-cache and
---weight-dtype fp8: the fp8-weight GEMMs of a token step of at most 16 rows on the skinny fp8-weight kernel) and, for
+--weight-dtype fp8: the fp8-weight GEMMs of a token step of at most 16 rows on the skinny fp8-weight kernel),
+--moe-skinny-w8 (with --moe-decode and --weight-dtype fp8-experts: the fp8 expert GEMMs of a step of a few token rows
+on the skinny grouped fp8-weight kernel) and, for
 ``run``, --past P (the caches are filled with random rows to length P before the timed steps).
 """
 from __future__ import annotations
@@ -95,6 +97,11 @@ def _common(ap: argparse.ArgumentParser) -> None:
                     help="with --kv-cache and --weight-dtype fp8 (bf16 activations): the e4m3-weight GEMMs of a token "
                          "step of at most ops.SKINNY_W8_MAX_ROWS rows run on the weight-streaming kernel of "
                          "ops.linear_skinny_w8 instead of the tiles of ops.linear_w8")
+    ap.add_argument("--moe-skinny-w8", action="store_true",
+                    help="with --moe-decode and --weight-dtype fp8-experts (bf16 activations): lifts --moe-decode's "
+                         "bf16-only rule, and both grouped expert launches of a step of at most "
+                         "ops.MOE_SKINNY_W8_MAX_ROWS token rows run on the weight-streaming kernel of "
+                         "ops.gemm_grouped_skinny_w8 instead of the tiles of ops.gemm_grouped_w8")
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="with --kv-cache: how the caches are stored: bf16, or fp8 (OCP e4m3 + one fp32 power-of-two "
                          "scale per position and KV head: (head_dim + 4) / (2 head_dim) of the bf16 bytes)")
@@ -112,7 +119,8 @@ def _plan(a, world: int, resume: Optional[str] = None):
                         placement=a.placement, tp=a.tp, resume=resume, sp=a.sp, weight_dtype=a.weight_dtype,
                         act_dtype=a.act_dtype, kv_cache=getattr(a, "kv_cache", None),
                         kv_dtype=getattr(a, "kv_dtype", "bf16"), moe_decode=getattr(a, "moe_decode", False),
-                        skinny_gemm=getattr(a, "skinny_gemm", False), skinny_w8=getattr(a, "skinny_w8", False))
+                        skinny_gemm=getattr(a, "skinny_gemm", False), skinny_w8=getattr(a, "skinny_w8", False),
+                        moe_skinny_w8=getattr(a, "moe_skinny_w8", False))
 
 
 def _has_kv(p) -> bool:
@@ -401,7 +409,7 @@ def cmd_generate(a) -> int:
     p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
                      kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk,
                      moe_decode=a.moe_decode, skinny_gemm=a.skinny_gemm, weight_dtype=a.weight_dtype,
-                     skinny_w8=a.skinny_w8)
+                     skinny_w8=a.skinny_w8, moe_skinny_w8=a.moe_skinny_w8)
     store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
     prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
@@ -511,8 +519,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--moe-decode", action="store_true", help="an MoE model's decode steps (see run --moe-decode)")
     g.add_argument("--skinny-gemm", action="store_true",
                    help="the dense GEMMs of the token step on the skinny kernel (see run --skinny-gemm)")
-    g.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
-                   help="GEMM weight storage (see run --weight-dtype)")
+    g.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp8-experts"],
+                   help="GEMM weight storage (see run --weight-dtype; fp8-experts: with --moe-skinny-w8)")
+    g.add_argument("--moe-skinny-w8", action="store_true",
+                   help="with --moe-decode and --weight-dtype fp8-experts: the fp8 expert GEMMs of the token step on "
+                        "the skinny grouped fp8-weight kernel (see run --moe-skinny-w8)")
     g.add_argument("--skinny-w8", action="store_true",
                    help="with --weight-dtype fp8: the fp8-weight GEMMs of the token step on the skinny fp8-weight "
                         "kernel (see run --skinny-w8)")

@@ -121,9 +121,10 @@ def check_kv_cache(cfg: ModelConfig, seq: int, kv_cache: int, tp: int = 1, sp: i
 
 
 def check_moe_decode(moe_decode: bool, cfg: ModelConfig, kv_cache: "int | None", weight_dtype: str = "bf16",
-                     prefill_chunk=None) -> None:
+                     prefill_chunk=None, moe_skinny_w8: bool = False) -> None:
     """What ``moe_decode=True`` (decode steps of an MoE model over the KV cache, the expert GEMMs
-    of a step of a few token rows on the skinny grouped kernel: ops.MOE_SKINNY_MAX_ROWS) needs of a plan."""
+    of a step of a few token rows on the skinny grouped kernel: ops.MOE_SKINNY_MAX_ROWS) needs of a plan.
+    ``moe_skinny_w8`` lifts the bf16-only rule for ``weight_dtype="fp8-experts"``, and for nothing else."""
     if not moe_decode:
         return
     if kv_cache is None:
@@ -131,12 +132,32 @@ def check_moe_decode(moe_decode: bool, cfg: ModelConfig, kv_cache: "int | None",
     if not cfg.n_experts:
         raise ValueError(f"moe_decode=True needs an MoE model; {cfg.name} has no experts (its decode steps need "
                          "no option)")
-    if weight_dtype != "bf16":
+    if weight_dtype != "bf16" and not (moe_skinny_w8 and weight_dtype == "fp8-experts"):
         raise ValueError(f"moe_decode=True takes weight_dtype='bf16' only, got {weight_dtype!r}: quantised experts "
                          "keep their own grouped kernels, which have no skinny form yet")
     if prefill_chunk is not None:
         raise ValueError("moe_decode=True does not combine with prefill_chunk: a chunk step's bit-identical repeat "
                          "has not been shown for the routing and combine launches of an MoE layer")
+
+
+def check_moe_skinny_w8(moe_skinny_w8: bool, moe_decode: bool, weight_dtype: str = "bf16",
+                        act_dtype: str = "bf16") -> None:
+    """What ``moe_skinny_w8=True`` (the e4m3 expert GEMMs of a decode step of at most
+    ops.MOE_SKINNY_W8_MAX_ROWS token rows on the weight-streaming kernel of
+    ops.gemm_grouped_skinny_w8) needs of a plan: ``moe_decode`` (hence a KV cache and an MoE model;
+    :func:`check_moe_decode` holds the rest of its rules) on fp8 experts with bf16 activations."""
+    if not moe_skinny_w8:
+        return
+    if not moe_decode:
+        raise ValueError("moe_skinny_w8=True needs moe_decode=True (an MoE model with kv_cache=C): the skinny grouped "
+                         "kernel is for the expert GEMMs of a decode step")
+    if weight_dtype != "fp8-experts":
+        raise ValueError(f"moe_skinny_w8=True takes weight_dtype='fp8-experts' only, got {weight_dtype!r}: it is the "
+                         "skinny form of the grouped e4m3-weight GEMM (bf16 experts take the skinny kernel under "
+                         "moe_decode alone; mxfp4 experts have no skinny form yet)")
+    if act_dtype == "fp8":
+        raise ValueError("moe_skinny_w8=True does not combine with act_dtype='fp8': W8A8 quantises the activations, "
+                         "and a skinny form of that grouped GEMM is a follow-up")
 
 
 def check_skinny_gemm(skinny_gemm: bool, kv_cache: "int | None", weight_dtype: str = "bf16") -> None:
@@ -279,7 +300,8 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
           tp: int = 1, sp: int = 1, weight_dtype: str = "bf16", act_dtype: str = "bf16",
           kv_cache: "int | None" = None,
           kv_dtype: str = "bf16", generate: bool = False,
-          moe_decode: bool = False) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
+          moe_decode: bool = False,
+          moe_skinny_w8: bool = False) -> Tuple[List[Task], Dict[str, ParamGroup], ModelConfig]:
     """``replicas`` independent requests (task ids prefixed ``r{k}/``) sharing weights;
     ``tp > 1`` splits every layer into tensor-parallel shards, ``sp > 1`` every token-wise
     node into sequence chunks (models/transforms.py). ``weight_dtype="fp8"``: the GEMM weights
@@ -301,7 +323,8 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
     ``generate=True`` (needs ``kv_cache`` and ``seq == 1``): every request's ``lm_head`` op carries
     ``attrs["sample"]``, the request's ordinal, and the executor samples the next token after it.
     ``moe_decode=True`` (needs ``kv_cache``, an MoE model and ``weight_dtype="bf16"``): lifts the
-    cache's refusal of MoE models (:func:`check_moe_decode`); the DAG is the model's own."""
+    cache's refusal of MoE models (:func:`check_moe_decode`); the DAG is the model's own.
+    ``moe_skinny_w8=True`` lets ``moe_decode`` take ``weight_dtype="fp8-experts"`` (:func:`check_moe_skinny_w8`)."""
     check_kv_dtype(kv_dtype, kv_cache)
     check_generate(generate, seq, kv_cache)
     known = WEIGHT_DTYPES + MX_WEIGHT_DTYPES + MX_EXPERT_WEIGHT_DTYPES
@@ -334,7 +357,8 @@ def build(model: str, batch: int = 1, seq: int = 512, replicas: int = 1, cost_mo
         if tp > 1 or sp > 1:
             raise ValueError(f"weight_dtype={weight_dtype!r} does not combine with tensor or sequence parallelism "
                              "(tp, sp > 1)")
-    check_moe_decode(moe_decode, cfg, kv_cache, weight_dtype)
+    check_moe_skinny_w8(moe_skinny_w8, moe_decode, weight_dtype, act_dtype)
+    check_moe_decode(moe_decode, cfg, kv_cache, weight_dtype, moe_skinny_w8=moe_skinny_w8)
     if kv_cache is not None:
         check_kv_cache(cfg, seq, kv_cache, tp, sp, moe_decode)
     tasks: List[Task] = []

@@ -1732,6 +1732,118 @@ def gemm_grouped_w8(x, qweights, scales, offsets, act=None, out=None, outs=None,
     return gemm_grouped(x, deq, offsets, act=act, out=out, outs=outs, a_rows=a_rows)
 
 
+# Token rows of a decode step of an fp8-experts plan with moe_skinny_w8=True up to which the
+# executor sends the two grouped expert launches of an MoE layer to the kernel of
+# gemm_grouped_skinny_w8.hip, set by the rule of MOE_SKINNY_MAX_ROWS: the largest bound such that
+# the captured decode step wins every alternating round at every B up to it
+# (benchmarks/bench_moe_decode.py --weight-dtype fp8-experts --step --max-rows 16;
+# profiles/moe_skinny_w8/step_bound_search.txt): mixtral-8x7b-1l at B = 1, 2, 4, 8, 16 x T 1 won 5 of
+# 5 rounds at every B, by 1.45x at one row down to 1.12x at sixteen. 16 is one pass of the kernel;
+# no step has more rows per expert in one pass, and none larger was measured.
+MOE_SKINNY_W8_MAX_ROWS = 16
+
+
+def grouped_skinny_w8_ok(N: int, K: int, act=None) -> bool:
+    """Does the skinny grouped fp8-weight kernel take an [N][K] e4m3 expert weight with this
+    activation? (gemm_grouped_skinny_w8_takes in gemm_grouped_skinny_w8.hip.)"""
+    a = ACT[act] if not isinstance(act, int) else act
+    if a not in (0, SWIGLU) or N <= 0 or K <= 0 or K % 32:
+        return False
+    return N % 32 == 0 if a == SWIGLU else N % 16 == 0
+
+
+# The instance rule of launch_gemm_grouped_skinny_w8, mirrored for the CPU back end; read off the
+# kernel table of profiles/moe_skinny_w8/kernels.txt (README, "fp8-expert skinny grouped GEMM").
+def grouped_skinny_w8_waves(N: int, K: int, act=None) -> int:
+    """Waves per workgroup ``gemm_grouped_skinny_w8`` launches with: 4, and 8 for a plain strip
+    from 64 slices of 128 k on (K > 8064)."""
+    a = ACT[act] if not isinstance(act, int) else act
+    return 4 if a == SWIGLU or (K + 127) // 128 < 64 else 8
+
+
+def grouped_skinny_w8_strip(N: int, K: int, act=None) -> int:
+    """Plain output columns per workgroup ``gemm_grouped_skinny_w8`` launches with: 32 (SwiGLU:
+    the 16-output gate/up pair)."""
+    a = ACT[act] if not isinstance(act, int) else act
+    return 16 if a == SWIGLU else 32
+
+
+def grouped_skinny_w8_nt(N: int, K: int, act=None) -> bool:
+    """Does ``gemm_grouped_skinny_w8`` load its weights with the streaming (nt) policy? No: it
+    lost every measured pair."""
+    return False
+
+
+def gemm_grouped_skinny_w8(x, qweights, scales, offsets, act=None, out=None, outs=None, w_ptrs=None, s_ptrs=None,
+                           out_ptrs=None, a_rows=None, waves=None, strip=None, nt=None):
+    """``gemm_grouped_w8`` for the at most 16 rows per expert of a decode step (GPU: the
+    weight-streaming kernel of gemm_grouped_skinny_w8.hip, grid = experts x column strips, fixed by
+    (E, N, strip) alone). Same arguments and results as ``gemm_grouped_w8``: expert e multiplies the
+    sorted rows [offsets[e], offsets[e+1]) of bf16 ``x`` (token rows ``a_rows[r]`` when given) by
+    ``qweights[e]`` (``float8_e4m3fn`` [N][K]), scales channel n by ``scales[e][n]`` (fp32 [N], any
+    positive values, applied once after the fp32 accumulation) and writes the rows at the same rows
+    of ``out`` or compactly into ``outs[e]``. ``act`` None or "swiglu" (rows of q AND scale
+    gate/up-interleaved in blocks of ``SWIGLU_BLOCK``), K % 32 == 0, N % 16 == 0 (SwiGLU:
+    N % 32 == 0); any other shape raises ``ValueError``. Any row counts are legal: an expert without
+    rows reads no weight byte, one with more than 16 takes further passes over its weight.
+    ``waves`` (4, 8), ``strip`` (16, 32 plain columns per workgroup) and ``nt`` force an instance;
+    None: the launcher's rule (:func:`grouped_skinny_w8_waves` / ``_strip`` / ``_nt``). CPU tensors
+    run ``gemm_grouped_w8``'s reference path."""
+    name = "gemm_grouped_skinny_w8"
+    a = ACT[act] if not isinstance(act, int) else act
+    E = len(qweights)
+    if E == 0 or len(scales) != E:
+        raise ValueError(f"{name}: at least one expert, and one scale tensor per expert weight")
+    if qweights[0].dim() != 2 or x.dim() != 2:
+        raise ValueError(f"{name}: x [rows][K] and expert weights [N][K]")
+    N, K = qweights[0].shape
+    if a not in (0, SWIGLU):
+        raise ValueError(f"{name}: act must be None or 'swiglu', not {act!r}")
+    if not grouped_skinny_w8_ok(N, K, a):
+        raise ValueError(f"{name}: N = {N}, K = {K} not taken: K % 32 == 0 and N % 16 == 0 (SwiGLU: N % 32 == 0)")
+    if waves not in (None, 4, 8):
+        raise ValueError(f"{name}: waves in {{4, 8}}, not {waves!r}")
+    if strip not in (None, 16, 32) or (strip == 32 and a == SWIGLU):
+        raise ValueError(f"{name}: strip is 16, or 32 without SwiGLU, not {strip!r}")
+    if x.shape[1] != K or any(tuple(q.shape) != (N, K) for q in qweights):
+        raise ValueError(f"{name}: every expert weight must be [N][K] with K = x.shape[1]")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: x must be bf16")
+    if any(q.dtype != torch.float8_e4m3fn for q in qweights):
+        raise ValueError(f"{name}: the weights must be float8_e4m3fn")
+    if any(s.dtype != torch.float32 or tuple(s.shape) != (N,) or not s.is_contiguous() for s in scales):
+        raise ValueError(f"{name}: every scale must be a contiguous fp32 [{N}] tensor")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        raise ValueError(f"{name}: rows of x must be contiguous and 16-byte aligned (row stride % 8 == 0)")
+    if any(not q.is_contiguous() or q.data_ptr() % 16 for q in qweights):
+        raise ValueError(f"{name}: expert weights must be contiguous and 16-byte aligned")
+    if offsets.numel() != E + 1 or offsets.dtype != torch.int32:
+        raise ValueError(f"{name}: offsets int32 [E+1]")
+    if a_rows is not None and a_rows.dtype != torch.int32:
+        raise ValueError(f"{name}: a_rows int32")
+    if (out is None) == (outs is None):
+        raise ValueError(f"{name}: exactly one of `out` and `outs`")
+    NO = N // 2 if a == SWIGLU else N
+    R = x.shape[0] if a_rows is None else a_rows.numel()
+    if out is not None and tuple(out.shape) != (R, NO):
+        raise ValueError(f"{name}: out must be [{R}][{NO}]")
+    if outs is not None and (len(outs) != E or any(o.dim() != 2 or o.shape[1] != NO for o in outs)):
+        raise ValueError(f"{name}: outs must be E tensors [cap][{NO}]")
+    if _gpu(x):
+        mk = lambda ts: torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=x.device)  # noqa: E731
+        if w_ptrs is None:
+            w_ptrs = mk(qweights)
+        if s_ptrs is None:
+            s_ptrs = mk(scales)
+        if outs is not None and out_ptrs is None:
+            out_ptrs = mk(outs)
+        ext().gemm_grouped_skinny_w8(x, list(qweights), list(scales), w_ptrs, s_ptrs, offsets, a, out,
+                                     list(outs) if outs is not None else [], out_ptrs, a_rows, int(waves or 0),
+                                     int(strip or 0), -1 if nt is None else int(bool(nt)))
+        return out if outs is None else outs
+    return gemm_grouped_w8(x, qweights, scales, offsets, act=a, out=out, outs=outs, a_rows=a_rows)
+
+
 def w4a8_grouped_configs() -> int:
     """Number of tile configurations of the grouped MXFP4 x fp8 GEMM (``gemm_grouped_w4a8(config=...)``)."""
     return int(ext().gemm_w4a8_grouped_num_configs())

@@ -196,8 +196,13 @@ class DAGExecutor:
                  trace: bool = False, debug: bool = False, model_name: Optional[str] = None,
                  input_parts: Optional[Dict[str, List[str]]] = None,
                  requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16",
-                 prefill_chunk: Optional[int] = None, skinny_gemm: bool = False, skinny_w8: bool = False):
+                 prefill_chunk: Optional[int] = None, skinny_gemm: bool = False, skinny_w8: bool = False,
+                 moe_skinny_w8: bool = False):
         self.tasks = {t.id: t for t in tasks}
+        # runtime.plan moe_skinny_w8=True (an fp8-experts plan with moe_decode): the two grouped e4m3
+        # expert launches of a step of at most ops.MOE_SKINNY_W8_MAX_ROWS token rows go to
+        # ops.gemm_grouped_skinny_w8 (_run_moe_batch); DLS_MOE_SKINNY=0 keeps the grouped W8 tiles.
+        self.moe_skinny_w8 = bool(moe_skinny_w8)
         # runtime.plan skinny_gemm=True: the dense bf16 GEMMs of a step of at most ops.SKINNY_MAX_ROWS
         # token rows go to ops.linear_skinny (_skinny_pick). DLS_SKINNY=0 turns the dispatch off (the
         # launches of the plan without the option), DLS_SKINNY=all takes every step of up to 16 rows
@@ -727,6 +732,17 @@ class DAGExecutor:
                 hq, hs = self._moe_q8(("h",), hbuf)
                 ops.gemm_grouped_w4a8(hq, hs, q2, s2, off, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4],
                                       rows_hint=max(1, R // E))
+                return
+            if (self.moe_skinny_w8 and MOE_SKINNY and self.kv_capacity is not None
+                    and R // K <= ops.MOE_SKINNY_W8_MAX_ROWS
+                    and ops.grouped_skinny_w8_ok(2 * F, x.shape[1], "swiglu")
+                    and ops.grouped_skinny_w8_ok(q2[0].shape[0], F)):
+                # a decode step of a few token rows: both launches stream the routed experts' e4m3
+                # bytes only (gemm_grouped_skinny_w8.hip), from the same cached pointer arrays
+                self._moe_skinny[i] = ("gate_up", "down")
+                ops.gemm_grouped_skinny_w8(x, q13, s13, off, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
+                                           a_rows=rows)
+                ops.gemm_grouped_skinny_w8(hbuf, q2, s2, off, outs=outs, w_ptrs=pt[2], s_ptrs=pt[3], out_ptrs=pt[4])
                 return
             ops.gemm_grouped_w8(x, q13, s13, off, act="swiglu", out=hbuf, w_ptrs=pt[0], s_ptrs=pt[1],
                                 rows_hint=max(1, R // E), a_rows=rows)

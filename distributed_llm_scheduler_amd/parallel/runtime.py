@@ -78,7 +78,7 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
          generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False,
-         skinny_gemm: bool = False, skinny_w8: bool = False) -> Plan:
+         skinny_gemm: bool = False, skinny_w8: bool = False, moe_skinny_w8: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -209,6 +209,17 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     than ``"fp8"``, ``act_dtype="fp8"``, and ``skinny_gemm=True`` together with it. The key enters
     ``Plan.args`` only when set.
 
+    ``moe_skinny_w8=True`` (with ``moe_decode=True`` and ``weight_dtype="fp8-experts"``; either
+    ``kv_dtype``, with or without ``generate``): lifts ``moe_decode``'s bf16-only rule for fp8
+    experts, and the executor sends both grouped expert launches of a step of at most
+    ``ops.MOE_SKINNY_W8_MAX_ROWS`` token rows to the weight-streaming kernel of
+    ``ops.gemm_grouped_skinny_w8`` instead of the tiles of ``ops.gemm_grouped_w8``
+    (``DLS_MOE_SKINNY=0``, any larger step and capped plans keep the tiles). The DAG, the
+    placement, the programs and the costs are those of the fp8-experts plan. Refused with
+    ``ValueError``: no ``moe_decode``, a ``weight_dtype`` other than ``"fp8-experts"`` (MXFP4
+    experts included), ``act_dtype="fp8"``; every other rule of ``moe_decode`` holds. The key
+    enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -246,9 +257,13 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_prefill_chunk(prefill_chunk, seq, kv_cache)
     if prefill_chunk is not None:  # (only when set, as generate)
         args["prefill_chunk"] = prefill_chunk
-    registry.check_moe_decode(moe_decode, registry.get_config(model), kv_cache, weight_dtype, prefill_chunk)
+    registry.check_moe_skinny_w8(moe_skinny_w8, moe_decode, weight_dtype, act_dtype)
+    registry.check_moe_decode(moe_decode, registry.get_config(model), kv_cache, weight_dtype, prefill_chunk,
+                              moe_skinny_w8=moe_skinny_w8)
     if moe_decode:  # (only when set, as generate)
         args["moe_decode"] = True
+    if moe_skinny_w8:  # (only when set, as skinny_w8)
+        args["moe_skinny_w8"] = True
     registry.check_skinny_w8(skinny_w8, kv_cache, weight_dtype, act_dtype, skinny_gemm)
     if skinny_w8:  # (only when set, as skinny_gemm)
         args["skinny_w8"] = True
@@ -270,7 +285,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
                 requests[f"r{k}/"] = (pre, j * batch, (j + 1) * batch)
     tasks, groups, cfg = registry.build(model, batch=mb_batch, seq=seq, replicas=n_req, cost_model=cost_model, tp=tp,
                                         sp=sp, weight_dtype=weight_dtype, act_dtype=act_dtype, kv_cache=kv_cache,
-                                        kv_dtype=kv_dtype, generate=generate, moe_decode=moe_decode)
+                                        kv_dtype=kv_dtype, generate=generate, moe_decode=moe_decode,
+                                        moe_skinny_w8=moe_skinny_w8)
     param_bytes = {pid: group_layout(g)[0] for pid, g in groups.items()}
 
     def place_under(caps_now: Sequence[float]) -> Plan:
@@ -480,6 +496,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["skinny_gemm"] = (saved.get("skinny_gemm", False), args.get("skinny_gemm", False))
     if saved.get("skinny_w8", False) != args.get("skinny_w8", False):
         mismatch["skinny_w8"] = (saved.get("skinny_w8", False), args.get("skinny_w8", False))
+    if saved.get("moe_skinny_w8", False) != args.get("moe_skinny_w8", False):
+        mismatch["moe_skinny_w8"] = (saved.get("moe_skinny_w8", False), args.get("moe_skinny_w8", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -819,4 +837,4 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
                        input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"),
                        prefill_chunk=p.args.get("prefill_chunk"), skinny_gemm=p.args.get("skinny_gemm", False),
-                       skinny_w8=p.args.get("skinny_w8", False))
+                       skinny_w8=p.args.get("skinny_w8", False), moe_skinny_w8=p.args.get("moe_skinny_w8", False))
