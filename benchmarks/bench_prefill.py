@@ -19,6 +19,10 @@
    the chunk path is not the faster in every pair at B 1, a 512-token prompt, Tc 128.
 
     python benchmarks/bench_prefill.py [--rounds 3] [--out DIR] [--skip-attention] [--skip-ttft] [--quick]
+                                       [--kv-dtype fp8 [--chunk-fp8]]
+
+``--kv-dtype fp8`` runs table 2 on fp8 caches, ``--chunk-fp8`` with the chunk attention that reads
+them directly (attn_chunk_fp8.hip; its kernel table is benchmarks/bench_chunk_fp8.py).
 
 Needs a GPU: there is no fallback.
 """
@@ -131,11 +135,12 @@ def attention_table(a):
     return ["chunk attention over the cache, us per call, median of alternating same-device rounds"] + lines + tail
 
 
-def ttft_row(B, L, Tc, rounds, C=8192, model="llama3-8b-1l"):
+def ttft_row(B, L, Tc, rounds, C=8192, model="llama3-8b-1l", kv_dtype="bf16", chunk_fp8=False):
     from distributed_llm_scheduler_amd.parallel import runtime
     from distributed_llm_scheduler_amd.parallel.executor import synthetic_tokens
 
-    p = runtime.plan(model, world=1, seq=1, batch=B, kv_cache=C, generate=True, prefill_chunk=Tc)
+    p = runtime.plan(model, world=1, seq=1, batch=B, kv_cache=C, generate=True, prefill_chunk=Tc, kv_dtype=kv_dtype,
+                     chunk_fp8=chunk_fp8)
     store = runtime.make_store(p, seed=0, device_init=runtime.device_init_ok(p, 0))
     # (autotune=False: the chunk step's GEMM shapes, M = B*Tc, run the kernels' own choice where the
     # tuning table has no entry; the token step's shapes are in the table)
@@ -185,7 +190,7 @@ def ttft_table(a):
                                             (1, 512, 512), (1, 4096, 512)]
     gate = None
     for B, L, Tc in rows:
-        line, faster = ttft_row(B, L, Tc, a.rounds)
+        line, faster = ttft_row(B, L, Tc, a.rounds, kv_dtype=a.kv_dtype, chunk_fp8=a.chunk_fp8)
         if (B, L, Tc) == (1, 512, 128):
             gate = faster
         print(line, flush=True)
@@ -198,7 +203,8 @@ def ttft_table(a):
             f"{'not measured' if gate is None else 'met' if gate else 'NOT met'}"]
     for x in tail:
         print(x, flush=True)
-    return ["time to the first generated token, llama3-8b-1l, C = 8192, ms"] + lines + tail, gate
+    what = f", kv_dtype {a.kv_dtype}" + (", chunk_fp8" if a.chunk_fp8 else "") if a.kv_dtype != "bf16" else ""
+    return [f"time to the first generated token, llama3-8b-1l, C = 8192{what}, ms"] + lines + tail, gate
 
 
 def main():
@@ -208,6 +214,10 @@ def main():
     ap.add_argument("--skip-attention", action="store_true")
     ap.add_argument("--skip-ttft", action="store_true")
     ap.add_argument("--quick", action="store_true", help="one T per shape, one row of the first-token table")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"], help="the caches of the first-token plan")
+    ap.add_argument("--chunk-fp8", action="store_true",
+                    help="with --kv-dtype fp8: the first-token plan's chunk attention reads the e4m3 caches itself "
+                         "(runtime.plan chunk_fp8=True)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_prefill.py needs a GPU")

@@ -502,6 +502,25 @@ void launch_attn_chunk(const ChunkAttnArgs& a, hipStream_t s);
 // out[b][r] = e4m3 cache[b][r] x scale[b][h][r] as bf16 for r < min(pos[b]+T, C); no other row is written
 void launch_kv_dequantize_rows(const void* cache, const float* scale, const int* pos, void* out, int B, int T, int C,
                                int n_kv_head, int D, hipStream_t s);
+// Chunk attention straight over e4m3 caches (attn_chunk_fp8.hip): the same rows against the same
+// keys as ChunkAttnArgs, K and V as stored (uint8 [B][C][n_kv_head*D], scales fp32
+// [B][n_kv_head][C]); no dequantise pass and no workspace.
+struct ChunkFp8Args {
+  const void* q; int ldq;  // bf16 [B*T][>= n_head*D]
+  const void* k_cache;     // e4m3 bytes [B][C][n_kv_head*D]
+  const void* v_cache;
+  const float* k_scale;    // fp32 [B][n_kv_head][C]
+  const float* v_scale;
+  void* o; int ldo;        // bf16 [B*T][>= n_head*D]
+  const int* pos;          // int32 [B], read by the kernel
+  int B, T, C, n_head, n_kv_head, D;
+  float scale;
+  int layout = 0;          // 0: attn_chunk_fp8_layout's choice; 12, 14, 22: NW query tiles x KS key groups as 10*NW + KS
+};
+// why the kernel does not take the shape, or null
+const char* attn_chunk_fp8_refusal(int T, int n_head, int n_kv_head, int D);
+int attn_chunk_fp8_layout(int B, int T, int n_head, int n_kv_head, int D, int layout);  // the layout a launch takes
+void launch_attn_chunk_fp8(const ChunkFp8Args& a, hipStream_t s);
 // pos[b] = min(pos[b] + T, max(limit[b], pos[b]))
 void launch_kv_advance(int* pos, const int* limit, int B, int T, hipStream_t s);
 

@@ -747,6 +747,41 @@ at::Tensor attention_chunk(const at::Tensor& q, const at::Tensor& k_cache, const
   return o;
 }
 
+// the same rows straight over e4m3 caches (attn_chunk_fp8.hip): no dequantise pass, no workspace
+at::Tensor attention_chunk_fp8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                               const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& pos, int64_t T,
+                               int64_t n_head, int64_t n_kv_head, int64_t head_dim, double scale,
+                               const c10::optional<at::Tensor>& out, int64_t layout) {
+  TORCH_CHECK(k_cache.dim() == 3, "caches must be [B][C][n_kv_head*head_dim]");
+  const int64_t B = k_cache.size(0), C = k_cache.size(1);
+  const char* why = attn_chunk_fp8_refusal((int)T, (int)n_head, (int)n_kv_head, (int)head_dim);
+  TORCH_CHECK(why == nullptr, "attention_chunk_fp8: ", why ? why : "", " (T ", T, ", heads ", n_head, "/", n_kv_head,
+              ", head_dim ", head_dim, ")");
+  TORCH_CHECK(layout == 0 || layout == 12 || layout == 14 || layout == 22,
+              "attention_chunk_fp8: layout must be 0, 12, 14 or 22");
+  TORCH_CHECK(B >= 1 && B <= 65535 && n_kv_head <= 65535 && C >= 1, "attention_chunk_fp8: batch / capacity");
+  TORCH_CHECK(check_caches(k_cache, v_cache, n_kv_head * head_dim, k_scale, v_scale, n_kv_head),
+              "attention_chunk_fp8: the kernel takes uint8 (e4m3) caches");
+  check_bf16(q, "q");
+  check_rows(q, "q");
+  TORCH_CHECK(q.size(0) == B * T && q.size(1) >= n_head * head_dim, "q must be [B*T][>= n_head*head_dim]");
+  check_i32(pos, B, "pos");
+  at::Tensor o = out.has_value() ? as2d(*out) : at::empty({B * T, n_head * head_dim}, q.options());
+  check_bf16(o, "out");
+  check_rows(o, "out");
+  TORCH_CHECK(o.size(0) == B * T && o.size(1) >= n_head * head_dim, "out must be [B*T][>= n_head*head_dim]");
+  ChunkFp8Args a{};
+  a.q = q.data_ptr(), a.ldq = (int)q.stride(0);
+  a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr();
+  a.k_scale = k_scale.data_ptr<float>(), a.v_scale = v_scale.data_ptr<float>();
+  a.o = o.data_ptr(), a.ldo = (int)o.stride(0);
+  a.pos = pos.data_ptr<int>();
+  a.B = (int)B, a.T = (int)T, a.C = (int)C, a.n_head = (int)n_head, a.n_kv_head = (int)n_kv_head;
+  a.D = (int)head_dim, a.scale = (float)scale, a.layout = (int)layout;
+  launch_attn_chunk_fp8(a, cur_stream());
+  return o;
+}
+
 void kv_advance(const at::Tensor& pos, const at::Tensor& limit, int64_t T) {
   const int64_t B = pos.numel();
   TORCH_CHECK(B >= 1 && T >= 0 && T < (1 << 30), "kv_advance: B >= 1, 0 <= T < 2^30");
@@ -2069,6 +2104,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_chunk", &attention_chunk, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("pos"),
         py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("scale"),
         py::arg("out") = py::none(), py::arg("variant") = 0);
+  m.def("attention_chunk_fp8", &attention_chunk_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("pos"), py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"),
+        py::arg("head_dim"), py::arg("scale"), py::arg("out") = py::none(), py::arg("layout") = 0);
+  m.def("attention_chunk_fp8_layout",
+        [](int64_t B, int64_t T, int64_t n_head, int64_t n_kv_head, int64_t D, int64_t layout) {
+          return attn_chunk_fp8_layout((int)B, (int)T, (int)n_head, (int)n_kv_head, (int)D, (int)layout);
+        },
+        py::arg("B"), py::arg("T"), py::arg("n_head"), py::arg("n_kv_head"), py::arg("head_dim"), py::arg("layout") = 0);
   m.def("kv_advance", &kv_advance, py::arg("pos"), py::arg("limit"), py::arg("T"));
   m.def("decode_prologue", &decode_prologue, py::arg("pos"), py::arg("tokens"), py::arg("tok_out"), py::arg("T"),
         py::arg("C"), py::arg("tables"), py::arg("outs"));

@@ -175,6 +175,7 @@ def _build_ops(kern, hdrs, hosts, host_hdrs, force, verbose, jobs) -> str:
     # the GEMMs keep the default (their accumulators only meet the VALU in the epilogue)
     per_file = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_chunk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                "attn_chunk_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 "attn_decode_fp8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                 # its only fp32 VALU math is the one-wave epilogue: scalar fp32 ops, no packed forms

@@ -20,6 +20,7 @@ Commands (defaults reproduce the reference's settings where one exists, SURVEY Â
             token ids, the steps and the tokens per second. ``--prefill-chunk Tc``: the prompts are
             consumed in chunk steps of Tc tokens per sequence (``runtime.plan(prefill_chunk=Tc)``); the
             line then also gives the chunk-step count and the time to the first generated token
+            (``--chunk-fp8``, with ``--kv-dtype fp8``: the chunk attention reads the e4m3 caches itself)
 
 Common options: --model, --devices (ignored under torchrun: WORLD_SIZE wins), --scheduler,
 --hbm-cap-gb, --cost-model {bytes,reference}, --seq, --batch, --replicas, --placement,
@@ -409,7 +410,7 @@ def cmd_generate(a) -> int:
     p = runtime.plan(a.model, world=1, scheduler=a.scheduler, cap_gb=a.hbm_cap_gb, batch=a.batch, seq=1,
                      kv_cache=a.kv_cache, kv_dtype=a.kv_dtype, generate=True, prefill_chunk=a.prefill_chunk,
                      moe_decode=a.moe_decode, skinny_gemm=a.skinny_gemm, weight_dtype=a.weight_dtype,
-                     skinny_w8=a.skinny_w8, moe_skinny_w8=a.moe_skinny_w8)
+                     skinny_w8=a.skinny_w8, moe_skinny_w8=a.moe_skinny_w8, chunk_fp8=a.chunk_fp8)
     store = runtime.make_store(p, seed=a.seed, device_init=gpu and runtime.device_init_ok(p, 0))
     ex = runtime.make_executor(p, 0, dev, store, use_graph=gpu and not a.no_graph)
     prompts = synthetic_tokens("@tokens", a.batch * a.prompt_len, p.cfg.vocab_size, a.seed).view(a.batch, -1).tolist()
@@ -516,6 +517,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     g.add_argument("--no-graph", action="store_true")
     g.add_argument("--prefill-chunk", type=int, default=None, metavar="Tc",
                    help="consume the prompts in chunk steps of Tc tokens per sequence (2 .. min(C, 1024))")
+    g.add_argument("--chunk-fp8", action="store_true",
+                   help="with --prefill-chunk and --kv-dtype fp8: the chunk step's attention reads the e4m3 caches "
+                        "itself (attn_chunk_fp8.hip) instead of dequantising them into a bf16 workspace first")
     g.add_argument("--moe-decode", action="store_true", help="an MoE model's decode steps (see run --moe-decode)")
     g.add_argument("--skinny-gemm", action="store_true",
                    help="the dense GEMMs of the token step on the skinny kernel (see run --skinny-gemm)")

@@ -240,6 +240,18 @@ def check_prefill_chunk(prefill_chunk, seq: int, kv_cache: "int | None") -> None
                          f"got {prefill_chunk!r}")
 
 
+def check_chunk_fp8(chunk_fp8: bool, kv_dtype: str, prefill_chunk) -> None:
+    """What ``chunk_fp8=True`` (a chunk step's attention on the e4m3 caches themselves,
+    ops.attention_chunk native=True) needs of a plan: fp8 caches and a chunk step."""
+    if not chunk_fp8:
+        return
+    if kv_dtype != "fp8":
+        raise ValueError(f"chunk_fp8=True needs kv_dtype='fp8', got {kv_dtype!r}: it is the chunk attention that reads "
+                         "e4m3 caches; bf16 caches run the bf16 kernel already")
+    if prefill_chunk is None:
+        raise ValueError("chunk_fp8=True needs prefill_chunk=Tc: it is an option of the chunk step")
+
+
 def sample_slices(B: int, V: int):
     """(workgroups per row, elements per workgroup) of the sampling kernel (csrc/kernels/sample.hip
     ``sample_slices``), for its workspace's bytes."""

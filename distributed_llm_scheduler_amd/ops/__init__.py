@@ -1094,8 +1094,25 @@ def attention_chunk_variant(B, T, n_head, variant=0):
     return ext().attention_chunk_variant(int(B), int(T), int(n_head), int(variant))
 
 
+CHUNK_FP8_LAYOUTS = (12, 14, 22)  # NW query tiles x KS key groups per workgroup as 10*NW + KS (14: head_dim 64 only)
+
+
+def attention_chunk_native_refusal(T, n_head, n_kv_head, head_dim) -> Optional[str]:
+    """Why the e4m3 chunk kernel (``attention_chunk(native=True)``) does not take a shape (None: it
+    does) — the rules of attn_chunk_fp8_refusal in attn_chunk_fp8.hip."""
+    if not 1 <= T <= CHUNK_MAX_T:
+        return "needs 1 <= T <= 1024"
+    if n_kv_head < 1 or n_head < n_kv_head or n_head % n_kv_head:
+        return "n_head must be a multiple of n_kv_head"
+    if n_head // n_kv_head > 64:
+        return "takes at most 64 query heads per KV head"
+    if head_dim not in (64, 128):
+        return "head_dim must be 64 or 128"
+    return None
+
+
 def attention_chunk(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, scale=None, out=None,
-                    k_scale=None, v_scale=None, workspace=None, variant=0):
+                    k_scale=None, v_scale=None, workspace=None, variant=0, native=False, layout=0):
     """Causal attention of a prompt chunk: the ``T`` queries of every sequence (q [B*T][>=
     n_head*head_dim], 1 <= T <= 1024, any n_head / n_kv_head) against its cache rows; query row
     ``b*T + t`` attends rows ``0 .. min(pos[b]+t, C-1)``. Runs after ``kv_append``, as
@@ -1109,10 +1126,27 @@ def attention_chunk(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, sc
     GPU: attn_chunk.hip (``variant``: 0 = chosen by block count, or one of ``CHUNK_VARIANTS``).
     With ``k_scale`` / ``v_scale`` the caches are fp8: ``kv_dequantize_rows`` fills ``workspace`` —
     two bf16 [B][C][n_kv_head*head_dim] buffers (K, V) allocated by the caller — and the bf16 kernel
-    runs on it. CPU: fp32 torch."""
+    runs on it. CPU: fp32 torch.
+    ``native=True`` (fp8 caches only, ``workspace`` must be None): the GPU path is one launch of
+    attn_chunk_fp8.hip, which reads the e4m3 bytes and the scales as they are stored — no
+    dequantise pass, no workspace, the query heads of a KV head packed into one workgroup
+    (``layout``: 0 = the launcher's choice, or one of ``CHUNK_FP8_LAYOUTS``). A shape it refuses
+    (:func:`attention_chunk_native_refusal`) raises RuntimeError. The CPU path is the same fp32 torch."""
     scale = scale if scale is not None else 1.0 / math.sqrt(head_dim)
     if k_cache.dim() != 3:
         raise RuntimeError("attention_chunk: caches must be [B][C][n_kv_head*head_dim]")
+    if native:
+        if k_scale is None or k_cache.dtype != torch.uint8:
+            raise RuntimeError("attention_chunk: native=True is the kernel of fp8 (uint8 e4m3) caches with k_scale / "
+                               "v_scale; bf16 caches take native=False")
+        if workspace is not None:
+            raise RuntimeError("attention_chunk: native=True reads the fp8 caches directly and takes no workspace")
+        if layout not in (0,) + CHUNK_FP8_LAYOUTS:
+            raise RuntimeError(f"attention_chunk: layout must be 0 or one of {CHUNK_FP8_LAYOUTS}")
+        why = attention_chunk_native_refusal(T, n_head, n_kv_head, head_dim)
+        if why is not None and _gpu(q):
+            raise RuntimeError(f"attention_chunk: native=True {why} (T {T}, heads {n_head}/{n_kv_head}, "
+                               f"head_dim {head_dim})")
     if not (1 <= T <= CHUNK_MAX_T and n_kv_head >= 1 and n_head % n_kv_head == 0):
         raise RuntimeError("attention_chunk: needs 1 <= T <= 1024 and n_head a multiple of n_kv_head "
                            f"(T {T}, heads {n_head}/{n_kv_head})")
@@ -1122,6 +1156,9 @@ def attention_chunk(q, k_cache, v_cache, pos, T, n_head, n_kv_head, head_dim, sc
     if fp8:
         if k_scale.shape[1] != n_kv_head:
             raise RuntimeError("attention_chunk: scales must be fp32 [B][n_kv_head][C]")
+        if _gpu(q) and native:
+            return ext().attention_chunk_fp8(q, k_cache, v_cache, k_scale, v_scale, pos, int(T), n_head, n_kv_head,
+                                             head_dim, float(scale), out, int(layout))
         if _gpu(q):
             if workspace is None or len(workspace) != 2:
                 raise ValueError("attention_chunk with fp8 caches needs workspace=(k, v): two bf16 buffers of the "

@@ -197,8 +197,11 @@ class DAGExecutor:
                  input_parts: Optional[Dict[str, List[str]]] = None,
                  requests: Optional[Dict[str, Tuple[str, int, int]]] = None, act_dtype: str = "bf16",
                  prefill_chunk: Optional[int] = None, skinny_gemm: bool = False, skinny_w8: bool = False,
-                 moe_skinny_w8: bool = False):
+                 moe_skinny_w8: bool = False, chunk_fp8: bool = False):
         self.tasks = {t.id: t for t in tasks}
+        # runtime.plan chunk_fp8=True (fp8 caches with prefill_chunk): a chunk step's attention reads
+        # the e4m3 caches itself (ops.attention_chunk native=True); no dequantisation workspace.
+        self.chunk_fp8 = bool(chunk_fp8)
         # runtime.plan moe_skinny_w8=True (an fp8-experts plan with moe_decode): the two grouped e4m3
         # expert launches of a step of at most ops.MOE_SKINNY_W8_MAX_ROWS token rows go to
         # ops.gemm_grouped_skinny_w8 (_run_moe_batch); DLS_MOE_SKINNY=0 keeps the grouped W8 tiles.
@@ -369,7 +372,7 @@ class DAGExecutor:
             if ins.op == "run":
                 ws = max(ws, self._workspace_bytes(ins))
         # (one slab for both step shapes: the chunk step's groups need Tc times the rows)
-        self._pp = plan_prefill(self.tasks, p, self.prefill_chunk) if self.prefill_chunk else None
+        self._pp = plan_prefill(self.tasks, p, self.prefill_chunk, self.chunk_fp8) if self.prefill_chunk else None
         ws = max(ws, 256) + (self._pp.ws_extra if self._pp is not None else 0)
         self._ws_full = torch.empty(max(ws, 256) + g, dtype=torch.uint8, device=dev)
         self.ws_slab = self._ws_full[:self._ws_full.numel() - g]
@@ -1777,10 +1780,11 @@ class DAGExecutor:
                 ops.kv_append(qkv[:, nh * D:(nh + nkv) * D], qkv[:, (nh + nkv) * D:], kc, vc, st["pos"], S, ks, vs)
                 if self._chunk_on:
                     f8 = None
-                    if ks is not None and self.gpu:  # the rank's one bf16 workspace, viewed as this layer's caches
+                    if ks is not None and self.gpu and not self.chunk_fp8:
+                        # the rank's one bf16 workspace, viewed as this layer's caches
                         f8 = tuple(w[:kc.numel()].view(kc.shape) for w in self._ck["f8"])
                     ops.attention_chunk(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o, k_scale=ks,
-                                        v_scale=vs, workspace=f8)
+                                        v_scale=vs, workspace=f8, native=self.chunk_fp8)
                 else:
                     ops.attention_decode(qkv[:, :nh * D], kc, vc, st["pos"], S, nh, nkv, D, out=o,
                                          workspace=self._kv_ws, k_scale=ks, v_scale=vs)
@@ -2945,6 +2949,15 @@ class DAGExecutor:
                 raise ValueError(f"kv_cache: the decode attention kernel takes head_dim "
                                  f"{' or '.join(map(str, ops.DECODE_HEAD_DIMS))}, this model has {bad[0]}; "
                                  f"such a plan runs on the CPU executor only")
+            if self.chunk_fp8:
+                for t in cached:
+                    a = t.op.attrs
+                    why = ops.attention_chunk_native_refusal(self.prefill_chunk or 1, a["n_head"], a["n_kv_head"],
+                                                             a["head_dim"])
+                    if why:
+                        raise ValueError(f"chunk_fp8: the e4m3 chunk attention kernel {why} ({t.id}: heads "
+                                         f"{a['n_head']}/{a['n_kv_head']}, head_dim {a['head_dim']}); such a plan "
+                                         f"runs on the CPU executor only")
         for t in self.tasks.values():  # host state of every request of the plan
             if t.op is not None and t.op.kind in ("embedding", "attention") and _kv_prefix(t.id) not in self._kv:
                 B, T = t.op.out_shape[0], t.op.out_shape[1]

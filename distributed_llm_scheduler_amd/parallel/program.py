@@ -1104,11 +1104,12 @@ def _request_prefix(tid: str) -> str:
     return tid.rsplit("/", 1)[0] + "/" if "/" in tid else ""
 
 
-def plan_prefill(tmap: Dict[str, Task], prog: Program, Tc: int) -> PrefillPlan:
+def plan_prefill(tmap: Dict[str, Task], prog: Program, Tc: int, chunk_fp8: bool = False) -> PrefillPlan:
     """The chunk step of one rank. It runs only the kernel groups that contain an attention task
     with a KV cache or an ancestor of one (the last layer's MLP, the final norm, the LM head and the
     sampler are skipped: a chunk step produces no logits), with ``Tc`` times the rows. Its arena is
-    planned by the activation planner over those groups."""
+    planned by the activation planner over those groups. ``chunk_fp8`` (runtime.plan): the chunk
+    attention reads the fp8 caches itself, so no ``@f8`` dequantisation buffers are planned."""
     pp = PrefillPlan(Tc=int(Tc))
     keep = set()
     stack = [t.id for t in tmap.values() if t.op is not None and t.op.kind == "attention" and "kv_cache" in t.op.attrs]
@@ -1166,7 +1167,7 @@ def plan_prefill(tmap: Dict[str, Task], prog: Program, Tc: int) -> PrefillPlan:
                     D = a["head_dim"]
                     need.append((pre, "cos_g", (B * pp.Tc, D // 2), "float32", 4 * B * pp.Tc * (D // 2)))
                     need.append((pre, "sin_g", (B * pp.Tc, D // 2), "float32", 4 * B * pp.Tc * (D // 2)))
-                if a.get("kv_dtype", "bf16") == "fp8":
+                if a.get("kv_dtype", "bf16") == "fp8" and not chunk_fp8:
                     f8 = max(f8, B * a["kv_cache"] * a["n_kv_head"] * a["head_dim"])
     if f8:  # one layer's bf16 K and V cache, shared by every layer of the rank
         need.append(("@f8", "k", (f8,), "bfloat16", 2 * f8))

@@ -78,7 +78,8 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
          residency: Optional[str] = None, merge_mb: int = 1, weight_dtype: str = "bf16",
          act_dtype: str = "bf16", kv_cache: Optional[int] = None, kv_dtype: str = "bf16",
          generate: bool = False, prefill_chunk: Optional[int] = None, moe_decode: bool = False,
-         skinny_gemm: bool = False, skinny_w8: bool = False, moe_skinny_w8: bool = False) -> Plan:
+         skinny_gemm: bool = False, skinny_w8: bool = False, moe_skinny_w8: bool = False,
+         chunk_fp8: bool = False) -> Plan:
     """Build the DAG of ``replicas`` requests of ``model``, place it on ``world`` GPUs with
     ``scheduler`` under a per-GPU cap of ``cap_gb`` (one value, or one per GPU — the
     reference's heterogeneous node splits) and lower it to per-rank programs.
@@ -220,6 +221,14 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     experts included), ``act_dtype="fp8"``; every other rule of ``moe_decode`` holds. The key
     enters ``Plan.args`` only when set.
 
+    ``chunk_fp8=True`` (with ``kv_dtype="fp8"`` and ``prefill_chunk``): a chunk step's attention
+    reads the e4m3 caches itself (``ops.attention_chunk(native=True)``, attn_chunk_fp8.hip) instead
+    of dequantising them into a bf16 workspace first, so the chunk step plans no such workspace and
+    ``Plan.prefill_bytes`` falls by its bytes. The DAG, the placement, the programs and the token
+    step are those of the plan without the option. Refused with ``ValueError``: a ``kv_dtype``
+    other than ``"fp8"``, no ``prefill_chunk``; an executor on a GPU refuses a model whose heads the
+    kernel does not take. The key enters ``Plan.args`` only when set.
+
     ``resume``: path of a placement saved by :func:`save_plan` — the saved decision (task
     order per GPU and the LOAD/EVICT trace) is reused instead of re-running the policy; the
     DAG is rebuilt from the saved arguments, which must match this call's.
@@ -270,6 +279,9 @@ def plan(model: str = "gpt2", world: int = 1, scheduler: str = "EFT", cap_gb: fl
     registry.check_skinny_gemm(skinny_gemm, kv_cache, weight_dtype)
     if skinny_gemm:  # (only when set, as generate: the executor's choice of kernel, nothing the DAG sees)
         args["skinny_gemm"] = True
+    registry.check_chunk_fp8(chunk_fp8, kv_dtype, prefill_chunk)
+    if chunk_fp8:  # (only when set, as skinny_w8)
+        args["chunk_fp8"] = True
     requests, input_parts = {}, {}
     n_req, mb_batch = replicas, batch
     if merge_mb > 1:
@@ -400,7 +412,7 @@ def _kv_over_cap(p: Plan, caps_gb: Sequence[float], prefill_chunk: Optional[int]
     prefill = [0] * p.world
     if prefill_chunk is not None:
         tmap = {t.id: t for t in p.tasks}
-        prefill = [plan_prefill(tmap, pr, prefill_chunk).total for pr in p.programs]
+        prefill = [plan_prefill(tmap, pr, prefill_chunk, p.args.get("chunk_fp8", False)).total for pr in p.programs]
         p.prefill_bytes = prefill
     for r, pr in enumerate(p.programs):
         cap = int(caps_gb[r] * 1e9)
@@ -498,6 +510,8 @@ def _resume(path: str, args: Dict, sched):
         mismatch["skinny_w8"] = (saved.get("skinny_w8", False), args.get("skinny_w8", False))
     if saved.get("moe_skinny_w8", False) != args.get("moe_skinny_w8", False):
         mismatch["moe_skinny_w8"] = (saved.get("moe_skinny_w8", False), args.get("moe_skinny_w8", False))
+    if saved.get("chunk_fp8", False) != args.get("chunk_fp8", False):
+        mismatch["chunk_fp8"] = (saved.get("chunk_fp8", False), args.get("chunk_fp8", False))
     if mismatch:
         raise ValueError(f"saved plan was made with different arguments: {mismatch}")
     return _ResumedSchedule(sched, doc), {k: list(v) for k, v in doc["schedule"].items()}
@@ -837,4 +851,5 @@ def make_executor(p: Plan, rank: int, device, store: Optional[ParamStore] = None
                        use_graph=use_graph, pg=pg, trace=trace, debug=debug, model_name=p.cfg.name, autotune=autotune,
                        input_parts=p.input_parts, requests=p.requests, act_dtype=p.args.get("act_dtype", "bf16"),
                        prefill_chunk=p.args.get("prefill_chunk"), skinny_gemm=p.args.get("skinny_gemm", False),
-                       skinny_w8=p.args.get("skinny_w8", False), moe_skinny_w8=p.args.get("moe_skinny_w8", False))
+                       skinny_w8=p.args.get("skinny_w8", False), moe_skinny_w8=p.args.get("moe_skinny_w8", False),
+                       chunk_fp8=p.args.get("chunk_fp8", False))
